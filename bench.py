@@ -9,6 +9,8 @@ of the SD-1.5 architecture (no network for checkpoints).
 
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
+    python bench.py ... --dump-outputs DIR    (also writes what each leg's last timed step computed, DIR/<name>.npy: two builds
+                                               run with the same arguments get the same inputs and can be compared output for output)
 
 N > 1: one process per GPU.  Started WITHOUT a launcher (`python bench.py --gpus 8`), this process touches no GPU and
 starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD (never an exec), relays its rank-0
@@ -52,6 +54,23 @@ HBM_PEAK_GBS = 8000.0
 # cross-attention core algorithmic bytes per U-Net sample (fp16): 2 B * (q + o: 2 N C, k + v: 2 T C) per layer,
 # layers: 5 x (N 4096, C 320), 5 x (1024, 640), 5 x (256, 1280), 1 x (64, 1280); T = 77
 XATTN_BYTES_PER_SAMPLE = 2 * sum(n_l * (2 * N * C + 2 * 77 * C) for n_l, N, C in ((5, 4096, 320), (5, 1024, 640), (5, 256, 1280), (1, 64, 1280)))
+# --dump-outputs: at most five arrays per run (three of the denoise leg, one per training leg), 12 MB each => <= 64 MB in all
+DUMP_ARRAY_BYTES = 12 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write each tensor as DIR/<name>.npy in float32 (float64 stays float64).  A tensor larger than DUMP_ARRAY_BYTES is written as a fixed
+    sample: the flattened elements at indices drawn with seed 0 (the same for the same shape), in increasing order."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        k = DUMP_ARRAY_BYTES // a.itemsize
+        if a.size > k:
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        print(f"[bench] {name}: {tuple(t.shape)} -> {os.path.join(dirname, name)}.npy ({a.size} values)", file=sys.stderr)
 
 
 def dist_context():
@@ -271,6 +290,8 @@ def run_train(args, ctx, dev, stage=1):
     elapsed = time.perf_counter() - t0
     extra_timed = dict(extra)                         # counts of the timed region only
     gc.enable()
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, {"train_loss" if stage == 1 else "train_stage2_loss": losses[-1]})   # what training_step returned last
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -505,9 +526,9 @@ def run_denoise(args, ctx, dev):
             eps = state["eps"]
         else:
             eps = unet_eps()
-        xp, _ = ops.cfg_ddim_step(eps, state["x"], scales[idx], float(sampler.ddim_alphas[index]),
-                                  float(sampler.ddim_alphas_prev[index]), True)
-        state["x"] = xp
+        xp, x0 = ops.cfg_ddim_step(eps, state["x"], scales[idx], float(sampler.ddim_alphas[index]),
+                                   float(sampler.ddim_alphas_prev[index]), True)
+        state["x"], state["pred_x0"], state["eps_last"] = xp, x0, eps
 
     def barrier():
         if world > 1 or launched:
@@ -555,6 +576,10 @@ def run_denoise(args, ctx, dev):
         barrier()
         elapsed = time.perf_counter() - t0
         finite = bool(torch.isfinite(state["x"]).all())
+        if args.dump_outputs and rank == 0:
+            # what the last timed step handed back (the passes below run more steps): the next latent, its x0 prediction, the U-Net's
+            # [cond ; uncond] epsilon
+            dump_outputs(args.dump_outputs, {"denoise_x_prev": state["x"], "denoise_pred_x0": state["pred_x0"], "denoise_eps": state["eps_last"]})
 
     if world > 1 or launched:
         import torch.distributed as dist
@@ -739,7 +764,12 @@ def main():
     ap.add_argument("--mode", choices=["all", "denoise", "train", "train2"], default="all",
                     help="all (default): the headline denoise line (BASELINE configs[1]) carrying the Stage-1 training leg "
                          "(configs[2]/[3]) as its `train` object; denoise / train: one leg only (train prints its own line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after each leg's timed steps, write what its last step computed as DIR/<name>.npy (float32, <= 64 MB in all): "
+                         "denoise_x_prev, denoise_pred_x0, denoise_eps (denoise leg), train_loss, train_stage2_loss (training legs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     ctx = dist_context()
     world, rank, local_rank, launched = ctx
     if args.gpus > 1 and not launched:
@@ -788,6 +818,7 @@ def main():
             import copy
             ref_args = copy.copy(args)
             ref_args.reference_pass_structure, ref_args.no_roofline, ref_args.train_steps = True, True, min(args.train_steps, 8)
+            ref_args.dump_outputs = None
             for res, stage in ((tr, 1), (tr2, 2)):
                 if isinstance(res, dict) and "error" not in res:
                     try:
