@@ -15,7 +15,14 @@ files or VAE weights, so every component can be passed in, and:
 * ``vae``: optional object with ``decode(latents / 0.18215) -> images in [-1, 1]`` (VAE decode is SURVEY.md 8f rank 3); without it
   ``forward`` returns the final latents ``[BS, 4, 64, 64]`` instead of PIL images.
 
-SDXL / SD3 / flux / img2img pipelines, LCM, U-Net ensembles and the ConsistentID encoder are out of scope (external packages)."""
+``pipeline_name="img2img"`` is the reference's img2img branch (diffusers' ``StableDiffusionImg2ImgPipeline`` with the DDIM scheduler,
+what ``adaface_translate.py`` runs): ``forward``'s first argument carries the input image(s) (one PIL image or a list of 1 or
+``out_image_count``; see ``img2img_images_u8``), ``vae`` must be an ``AutoencoderKL`` (encoder + decoder), and ``ref_img_strength``
+picks how many of the last steps of the schedule run (``DDIMSampler.img2img_steps``).  The images are encoded once
+(``LatentDiffusion.img2img_latents``: two fused kernels around the VAE encoder) and denoised by ``DDIMSampler.sample_img2img``.
+
+SDXL / SD3 / flux pipelines, LCM, other schedulers, inpainting, U-Net ensembles and the ConsistentID encoder are out of scope
+(external packages)."""
 import re
 import zlib
 
@@ -29,6 +36,33 @@ from ..ldm.models.diffusion.ddpm import LatentDiffusion
 from .arc2face_models import CLIPTextModelWrapper, clip_text_config
 from .face_id_to_ada_prompt import Arc2Face_ID2AdaPrompt
 from .subj_basis_generator import CLIP_BOS, CLIP_EOS, CLIP_IDS
+
+
+def img2img_images_u8(images, out_image_count):
+    """img2img input preparation on the host: one PIL image or a list of 1 or ``out_image_count`` images, all of one size, converted
+    to RGB; a side that is not a multiple of 64 is resized down to one (LANCZOS; the U-Net needs a latent divisible by 8).
+    Returns uint8 [B_img, H, W, 3] on the CPU."""
+    from PIL import Image
+    imgs = list(images) if isinstance(images, (list, tuple)) else [images]
+    if len(imgs) not in (1, out_image_count):
+        raise ValueError(f"img2img takes 1 or out_image_count = {out_image_count} input images, got {len(imgs)}")
+    for im in imgs:
+        if not isinstance(im, Image.Image):
+            raise ValueError(f"img2img input images must be PIL images, got {type(im).__name__}")
+    sizes = {im.size for im in imgs}
+    if len(sizes) != 1:
+        raise ValueError(f"img2img input images must all have the same size, got {sorted(sizes)}")
+    w, h = imgs[0].size
+    if w < 64 or h < 64:
+        raise ValueError(f"img2img input images must be at least 64 x 64 pixels, got {w} x {h}")
+    w64, h64 = w // 64 * 64, h // 64 * 64
+    arrs = []
+    for im in imgs:
+        im = im.convert("RGB")
+        if (w64, h64) != (w, h):
+            im = im.resize((w64, h64), resample=Image.LANCZOS)
+        arrs.append(np.asarray(im, dtype=np.uint8))
+    return torch.from_numpy(np.stack(arrs))
 
 
 class WordTokenizer:
@@ -88,8 +122,9 @@ class AdaFaceWrapper(nn.Module):
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None):
         super().__init__()
-        if pipeline_name not in ("text2img", None):
-            raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img path (and None = face encoder only) is built")
+        if pipeline_name not in ("text2img", "img2img", None):
+            raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img and img2img paths (and None = face encoder only) "
+                                      "are built")
         if list(adaface_encoder_types) != ["arc2face"]:
             raise NotImplementedError("only the Arc2Face ID encoder is in scope (ConsistentID needs an external package)")
         if use_lcm or default_scheduler_name != "ddim":
@@ -275,6 +310,12 @@ class AdaFaceWrapper(nn.Module):
                 repeat_prompt_for_each_encoder=True, verbose=False):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
+        if self.pipeline_name == "img2img":
+            if self.vae is None or not hasattr(self.vae, "encode_q_sample"):
+                raise ValueError("the img2img pipeline encodes its input images: it needs an AutoencoderKL (encoder + decoder) as vae, "
+                                 f"got {type(self.vae).__name__ if self.vae is not None else None}")
+            images_u8 = img2img_images_u8(noise, out_image_count)
+            DDIMSampler(self.ldm).img2img_steps(self.num_inference_steps, ref_img_strength)    # refuse a bad strength before any work
         if prompt_embeds is None:
             pe, ne, _, _ = self.encode_prompt(prompt, negative_prompt, placeholder_tokens_pos=placeholder_tokens_pos,
                                               ablate_prompt_only_placeholders=ablate_prompt_only_placeholders,
@@ -288,15 +329,25 @@ class AdaFaceWrapper(nn.Module):
             raise ValueError("prompt_embeds must be a 2- or 4-tuple")
         pe = pe.repeat(out_image_count, 1, 1)
         ne = None if ne is None else ne.repeat(out_image_count, 1, 1)
-        noise = noise.to(device=self.device, dtype=torch.float32)
         self.ldm.to(self.device)
         sampler = DDIMSampler(self.ldm)
         cond = (pe, [prompt or ""] * out_image_count, {})
         uncond = None if ne is None else (ne, [negative_prompt or self.negative_prompt] * out_image_count, {})
+        if self.pipeline_name == "img2img":
+            _, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
+            x_t = self.ldm.img2img_latents(images_u8.to(self.device), out_image_count, t_first, generator=generator,
+                                           first_stage_model=self.vae)
+            latents, _ = sampler.sample_img2img(self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond,
+                                                guidance_scale=guidance_scale, unconditional_conditioning=uncond)
+            return self._to_pil(latents)
+        noise = noise.to(device=self.device, dtype=torch.float32)
         latents, _ = sampler.sample(self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise,
                                     verbose=False, guidance_scale=guidance_scale, unconditional_conditioning=uncond)
         if self.vae is None:
             return latents
+        return self._to_pil(latents)
+
+    def _to_pil(self, latents):
         images = self.vae.decode(latents / 0.18215)
         images = ((images.float() / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
         from PIL import Image

@@ -126,6 +126,57 @@ __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __res
   xt[i] = sa[b] * x0[i] + sb[b] * noise[i];
 }
 
+// img2img input: uint8 RGB [B,H,W,3] -> the encoder's conv_in layout fp16 [B,H,W,8], x = (v / 255) * 2 - 1 in fp32 (rounded once to
+// fp16), channels 3..7 zero.  One pixel per thread, one 16-byte store.
+__global__ __launch_bounds__(256) void image_u8_kernel(const unsigned char* __restrict__ img, half_t* __restrict__ out, long npix) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= npix) return;
+  const unsigned char* s = img + p * 3;
+  half8_t o;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c] = (half_t)(((float)s[c] / 255.0f) * 2.0f - 1.0f);
+#pragma unroll
+  for (int c = 3; c < 8; ++c) o[c] = (half_t)0;
+  *reinterpret_cast<half8_t*>(out + p * 8) = o;
+}
+
+// img2img latents: per latent pixel of image b, moments = quant_conv(h) (8 x 8 fp32 + bias), z = scale (mean + exp(0.5 clamp(logvar,
+// -30, 20)) n_post), and for every output j = b + r B_img:  x_t[j] = sa z + sb n_fwd[j].  h NHWC fp16 [B_img,hh,ww,8]; n_post fp32
+// NCHW [B_img,4,hh,ww]; n_fwd, x_t fp32 NCHW [B_out,4,hh,ww].  The 72 weights are wave-uniform loads.
+__global__ __launch_bounds__(256) void vae_latents_q_sample_kernel(const half_t* __restrict__ h, const float* __restrict__ qw,
+                                                                   const float* __restrict__ qb, const float* __restrict__ n_post,
+                                                                   const float* __restrict__ n_fwd, float scale, float sa, float sb,
+                                                                   float* __restrict__ x_t, int B_img, int reps, long hw) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B_img * hw) return;
+  const int b = (int)(i / hw);
+  const long p = i - (long)b * hw;
+  const half8_t v = *reinterpret_cast<const half8_t*>(h + i * 8);
+  float x[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) x[k] = (float)v[k];
+  float z[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    float mean = qb[c], logvar = qb[4 + c];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      mean += qw[c * 8 + k] * x[k];
+      logvar += qw[(4 + c) * 8 + k] * x[k];
+    }
+    logvar = fminf(fmaxf(logvar, -30.0f), 20.0f);
+    z[c] = scale * (mean + expf(0.5f * logvar) * n_post[((long)b * 4 + c) * hw + p]);
+  }
+  for (int r = 0; r < reps; ++r) {
+    const long j = (long)b + (long)r * B_img;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long o = (j * 4 + c) * hw + p;
+      x_t[o] = sa * z[c] + sb * n_fwd[o];
+    }
+  }
+}
+
 __global__ void silu_kernel(const half_t* __restrict__ x, half_t* __restrict__ y, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) y[i] = (half_t)af_silu((float)x[i]);
@@ -182,6 +233,29 @@ extern "C" int af_q_sample(const void* x0, const void* noise, const void* sa, co
   hipLaunchKernelGGL(q_sample_kernel, grid1d((long)B * per), dim3(256), 0, (hipStream_t)stream, (const float*)x0,
                      (const float*)noise, (const float*)sa, (const float*)sb, (float*)xt, B, (long)per);
   return af_check_launch("af_q_sample");
+}
+
+extern "C" int af_image_u8_to_nhwc_f16(const void* img, void* out, int B, int H, int W, void* stream) {
+  AF_REQUIRE(img && out && B > 0 && H > 0 && W > 0, "af_image_u8_to_nhwc_f16: bad argument");
+  AF_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "af_image_u8_to_nhwc_f16: out must be 16-byte aligned");
+  const long npix = (long)B * H * W;
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  hipLaunchKernelGGL(image_u8_kernel, grid1d(npix), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)img, (half_t*)out, npix);
+  return af_check_launch("af_image_u8_to_nhwc_f16");
+}
+
+extern "C" int af_vae_latents_q_sample(const void* h, const void* qw, const void* qb, const void* n_post, const void* n_fwd, float scale,
+                                       float sa, float sb, void* x_t, int B_img, int B_out, int hh, int ww, void* stream) {
+  AF_REQUIRE(h && qw && qb && n_post && n_fwd && x_t && B_img > 0 && B_out > 0 && hh > 0 && ww > 0,
+             "af_vae_latents_q_sample: bad argument");
+  AF_REQUIRE(B_out % B_img == 0, "af_vae_latents_q_sample: B_out must be a multiple of B_img");
+  AF_REQUIRE((reinterpret_cast<uintptr_t>(h) & 15) == 0, "af_vae_latents_q_sample: h must be 16-byte aligned");
+  const long hw = (long)hh * ww;
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  hipLaunchKernelGGL(vae_latents_q_sample_kernel, grid1d((long)B_img * hw), dim3(256), 0, (hipStream_t)stream, (const half_t*)h,
+                     (const float*)qw, (const float*)qb, (const float*)n_post, (const float*)n_fwd, scale, sa, sb, (float*)x_t, B_img,
+                     B_out / B_img, hw);
+  return af_check_launch("af_vae_latents_q_sample");
 }
 
 // dS = P * (dP - rowsum(P * dP)): the softmax backward of the VAE decoder's single-head attention (rows like af_softmax_rows)

@@ -94,6 +94,45 @@ class DDIMSampler:
                 intermediates["pred_x0"].append(pred_x0)
         return img, intermediates
 
+    def img2img_steps(self, S, strength):
+        """(n, t_first) of an img2img run over the S-step uniform schedule (diffusers' StableDiffusionImg2ImgPipeline.get_timesteps):
+        n = min(int(S * strength), S) steps, the last n of the schedule, starting from the latent noised to ddim_timesteps[n - 1]."""
+        if not 0 < strength <= 1:
+            raise ValueError(f"img2img strength must be in (0, 1], got {strength}")
+        n = min(int(S * strength), S)
+        if n == 0:
+            raise ValueError(f"img2img strength {strength} with {S} steps leaves no denoising step (int({S} * {strength}) = 0)")
+        ddim_timesteps = make_ddim_timesteps("uniform", S, self.ddpm_num_timesteps, verbose=False)
+        return n, int(ddim_timesteps[n - 1])
+
+    @torch.no_grad()
+    def sample_img2img(self, S, strength, batch_size, x_t, conditioning, guidance_scale=1.0, unconditional_conditioning=None,
+                       callback=None, img_callback=None, log_every_t=100):
+        """Denoise x_t (noised to img2img_steps(S, strength)[1], e.g. by LatentDiffusion.img2img_latents) through the last n steps
+        of the S-step schedule: indices n-1 .. 0 through p_sample_ddim, guidance per step from guide_scales(n, guidance_scale).
+        Returns (latents, intermediates) like sample()."""
+        n, _ = self.img2img_steps(S, strength)
+        self.make_schedule(ddim_num_steps=S, ddim_eta=0.0, verbose=False)
+        device = self.model.betas.device
+        if x_t.shape[0] != batch_size:
+            raise ValueError(f"x_t holds {x_t.shape[0]} latents, batch_size is {batch_size}")
+        img = x_t.to(torch.float32).contiguous()
+        intermediates = {"x_inter": [img], "pred_x0": [img]}
+        # one step: the first scale of the annealing rule (guide_scales divides by n - 1)
+        scales = self.guide_scales(n, guidance_scale) if n > 1 else self.guide_scales(2, guidance_scale)[:1]
+        for i, index in enumerate(range(n - 1, -1, -1)):
+            ts = torch.full((batch_size,), int(self.ddim_timesteps[index]), device=device, dtype=torch.long)
+            img, pred_x0 = self.p_sample_ddim(img, conditioning, ts, index=index, guidance_scale=scales[i],
+                                              unconditional_conditioning=unconditional_conditioning)
+            if callback:
+                callback(i)
+            if img_callback:
+                img_callback(pred_x0, i)
+            if index % log_every_t == 0 or index == n - 1:
+                intermediates["x_inter"].append(img)
+                intermediates["pred_x0"].append(pred_x0)
+        return img, intermediates
+
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, guidance_scale=1.0, unconditional_conditioning=None, **kwargs):
         """One DDIM step (ddim.py:223-302, eta = 0)."""

@@ -381,6 +381,29 @@ class LatentDiffusion(CompReconLossesMixin, nn.Module):
         z = mean + torch.exp(0.5 * logvar) * torch.randn(mean.shape, device=mean.device, dtype=mean.dtype, generator=generator)
         return self.scale_factor * z
 
+    @torch.no_grad()
+    def img2img_latents(self, images_u8, out_count, t, generator=None, first_stage_model=None):
+        """The img2img start latents (diffusers' StableDiffusionImg2ImgPipeline.prepare_latents with this scale factor): uint8 RGB
+        [B_img, H, W, 3] -> x_t fp32 [out_count, 4, H/8, W/8] noised to timestep t.  Each image is encoded once; output j uses image
+        j % B_img and shares its posterior sample.  Noise: n_post [B_img, 4, h, w] first, then n_fwd [out_count, 4, h, w], both
+        torch.randn on the generator's device (the default CUDA generator when None), moved to the model's device.
+        ``first_stage_model``: an AutoencoderKL to use instead of ``self.first_stage_model``."""
+        vae = first_stage_model if first_stage_model is not None else self.first_stage_model
+        if vae is None or not hasattr(vae, "encode_q_sample"):
+            raise ValueError("img2img needs a first-stage model with an encoder (AutoencoderKL); "
+                             f"got {type(vae).__name__ if vae is not None else None}")
+        dev = vae.quant_conv.weight.device
+        B_img, H, W, _ = images_u8.shape
+        if out_count % B_img != 0:
+            raise ValueError(f"out_count {out_count} is not a multiple of the image count {B_img}")
+        lat = (4, H // 8, W // 8)
+        gdev = generator.device if generator is not None else dev
+        n_post = torch.randn((B_img,) + lat, generator=generator, device=gdev).to(dev)
+        n_fwd = torch.randn((out_count,) + lat, generator=generator, device=gdev).to(dev)
+        t = int(t)
+        sa, sb = float(self.sqrt_alphas_cumprod[t]), float(self.sqrt_one_minus_alphas_cumprod[t])
+        return vae.encode_q_sample(images_u8.to(dev).contiguous(), n_post.contiguous(), n_fwd.contiguous(), self.scale_factor, sa, sb)
+
     def q_sample(self, x_start, t, noise=None):
         noise = torch.randn_like(x_start) if noise is None else noise
         sa = self.sqrt_alphas_cumprod[t]

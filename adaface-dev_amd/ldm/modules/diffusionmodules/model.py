@@ -492,3 +492,24 @@ class AutoencoderKL(AutoencoderKLDecoder):
         moments = self.quant_conv(self.encoder(x, mask).float())          # quant_conv: 8 -> 8 channels, 1x1 (plain af_gemm)
         mean, logvar = torch.chunk(moments.float(), 2, dim=1)
         return mean, torch.clamp(logvar, -30.0, 20.0)
+
+    def _qc_pack(self):
+        """quant_conv as the fp32 (weight [8 out, 8 in], bias [8]) pair that af_vae_latents_q_sample reads."""
+        c = self.quant_conv
+        key = (c.weight._version, c.bias._version, c.weight.data_ptr())
+        if key != getattr(self, "_qc_key", None):
+            w = c.weight.detach().float().reshape(c.out_channels, c.in_channels).contiguous()
+            self._qc, self._qc_key = (w, c.bias.detach().float().contiguous()), key
+        return self._qc
+
+    @torch.no_grad()
+    def encode_q_sample(self, images_u8, n_post, n_fwd, scale, sa, sb):
+        """img2img start latents: uint8 RGB [B_img, H, W, 3] on the device -> x_t fp32 [B_out, 4, H/8, W/8] =
+        sa * scale * (mean + exp(0.5 logvar) * n_post) + sb * n_fwd, output j from image j % B_img (n_post [B_img, 4, H/8, W/8],
+        n_fwd [B_out, 4, H/8, W/8] fp32).  Three launch groups: af_image_u8_to_nhwc_f16, the encoder, af_vae_latents_q_sample."""
+        _require_cuda(self.quant_conv.weight, "AutoencoderKL")
+        if self.quant_conv.in_channels != 8 or self.quant_conv.out_channels != 8:
+            raise NotImplementedError("encode_q_sample needs the z_channels = embed_dim = 4 first stage (8 moment channels)")
+        h = self.encoder.hip(ops.image_u8_to_nhwc_f16(images_u8))
+        qw, qb = self._qc_pack()
+        return ops.vae_latents_q_sample(h, qw, qb, n_post, n_fwd, scale, sa, sb, n_fwd.shape[0])

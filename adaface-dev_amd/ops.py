@@ -943,6 +943,40 @@ def q_sample(x0: torch.Tensor, noise: torch.Tensor, sa: torch.Tensor, sb: torch.
     return xt
 
 
+def image_u8_to_nhwc_f16(img_u8: torch.Tensor) -> torch.Tensor:
+    """uint8 RGB [B, H, W, 3] -> fp16 [B, H, W, 8] = (v / 255) * 2 - 1 in channels 0-2, zeros in 3-7 (the VAE encoder's input)."""
+    if img_u8.dtype != torch.uint8 or not img_u8.is_cuda or not img_u8.is_contiguous():
+        raise RuntimeError(f"image_u8_to_nhwc_f16: expected a contiguous uint8 device tensor, got {img_u8.dtype} {img_u8.device}")
+    if img_u8.dim() != 4 or img_u8.shape[3] != 3:
+        raise RuntimeError(f"image_u8_to_nhwc_f16: expected [B, H, W, 3], got {tuple(img_u8.shape)}")
+    B, H, W, _ = img_u8.shape
+    out = torch.empty((B, H, W, 8), dtype=F16, device=img_u8.device)
+    _lib.check(_lib.lib().af_image_u8_to_nhwc_f16(_p(img_u8), _p(out), B, H, W, _stream()), "af_image_u8_to_nhwc_f16")
+    return out
+
+
+def vae_latents_q_sample(h: torch.Tensor, qw: torch.Tensor, qb: torch.Tensor, n_post: torch.Tensor, n_fwd: torch.Tensor, scale: float,
+                         sa: float, sb: float, out_count: int) -> torch.Tensor:
+    """Encoder output h fp16 [B_img, hh, ww, 8] -> x_t fp32 [out_count, 4, hh, ww]: quant_conv (qw fp32 [8, 8] out x in, qb fp32 [8]),
+    posterior sample z = scale (mean + exp(0.5 clamp(logvar, -30, 20)) n_post), then sa z + sb n_fwd.  Output j uses image
+    j % B_img; n_post fp32 [B_img, 4, hh, ww], n_fwd fp32 [out_count, 4, hh, ww]."""
+    _chk_f16(h, "vae_latents_q_sample.h")
+    if h.dim() != 4 or h.shape[3] != 8:
+        raise RuntimeError(f"vae_latents_q_sample: h must be [B, hh, ww, 8], got {tuple(h.shape)}")
+    B_img, hh, ww, _ = h.shape
+    want = {"qw": (qw, (8, 8)), "qb": (qb, (8,)), "n_post": (n_post, (B_img, 4, hh, ww)), "n_fwd": (n_fwd, (out_count, 4, hh, ww))}
+    for name, (t, shape) in want.items():
+        if t.dtype != torch.float32 or t.device != h.device or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise RuntimeError(f"vae_latents_q_sample.{name}: expected contiguous fp32 {shape} on {h.device}, got {t.dtype} "
+                               f"{tuple(t.shape)} on {t.device}")
+    if out_count <= 0 or out_count % B_img != 0:
+        raise RuntimeError(f"vae_latents_q_sample: out_count {out_count} is not a positive multiple of the image count {B_img}")
+    x_t = torch.empty((out_count, 4, hh, ww), dtype=torch.float32, device=h.device)
+    _lib.check(_lib.lib().af_vae_latents_q_sample(_p(h), _p(qw), _p(qb), _p(n_post), _p(n_fwd), float(scale), float(sa), float(sb),
+                                                  _p(x_t), B_img, out_count, hh, ww, _stream()), "af_vae_latents_q_sample")
+    return x_t
+
+
 # ----------------------------------------------------------------------------- backward ops
 def groupnorm_train(x, gamma, beta, eps, silu, *, x2=None, groups=32):
     """groupnorm() that also returns the (mean, rstd) statistics fp32 [B, groups, 2] for the backward."""

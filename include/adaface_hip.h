@@ -374,6 +374,16 @@ int af_cfg_ddim_step(const void* eps2, const void* x, void* x_prev, void* pred_x
 /* q_sample (ldm/models/diffusion/ddpm.py:395-398): x_t = sa[b] x0 + sb[b] noise, fp32, per-sample scalars */
 int af_q_sample(const void* x0, const void* noise, const void* sa, const void* sb, void* xt, int B, int64_t per,
                 void* stream);
+/* img2img input (diffusers' image preprocessing): img uint8 [B,H,W,3] (RGB, as PIL hands it over) -> out fp16 [B,H,W,8], the VAE
+ * encoder's conv_in layout: channels 0-2 = (v / 255) * 2 - 1 computed in fp32 and rounded once, channels 3-7 written as 0.
+ * out 16-byte aligned; any H, W.                                                                                             */
+int af_image_u8_to_nhwc_f16(const void* img, void* out, int B, int H, int W, void* stream);
+/* img2img latents from the encoder's conv_out output, one launch: h fp16 NHWC [B_img,hh,ww,8] (16-byte aligned);
+ * moments = qw h + qb (quant_conv: qw fp32 [8 out][8 in] row-major, qb fp32 [8]); mean = moments[0:4],
+ * logvar = clamp(moments[4:8], -30, 20); z = scale (mean + exp(0.5 logvar) n_post), n_post fp32 NCHW [B_img,4,hh,ww];
+ * x_t = sa z + sb n_fwd, n_fwd / x_t fp32 NCHW [B_out,4,hh,ww]; output j reads image j % B_img.  B_out % B_img == 0.        */
+int af_vae_latents_q_sample(const void* h, const void* qw, const void* qb, const void* n_post, const void* n_fwd, float scale, float sa,
+                            float sb, void* x_t, int B_img, int B_out, int hh, int ww, void* stream);
 
 /* y = x * sigmoid(x), fp16 (nn.SiLU on the time embedding, openaimodel.py:219-220) */
 int af_silu_f16(const void* x, void* y, int64_t n, void* stream);
