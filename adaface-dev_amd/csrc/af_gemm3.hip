@@ -838,7 +838,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSLOT == 2) ? 2 
   //     products only reach output rows / columns the epilogue drops (m >= M, n >= N);
   //   * 3x3 taps keep a per-lane 64-bit pixel pointer per source; a stage adds the tap's scalar offset and selects the zero page for taps that
   //     fall outside the image (the nearest-x2 gather keeps the per-stage arithmetic: its tap offset depends on the lane's pixel parity).
-  // Byte offsets are 32-bit: the host routes tensors of 2 GB and more to the register-staged kernel.
+  // Byte offsets are 32-bit: the host routes operands of 4 GiB (2^32 bytes) and more to the register-staged kernel.
   unsigned w_off[WPW];
 #pragma unroll
   for (int j = 0; j < WPW; ++j) {
@@ -1791,12 +1791,14 @@ static int conv3h_variant(const af_gemm_desc* d) {
   if (d->c3 || d->c4) {                                            // K tail (round 6): plain rows of a3 | a4 on the output grid, whole 64-column stages
     if (!n160 || d->c3 <= 0 || d->c3 % 64 != 0 || d->c4 < 0 || d->c4 % 64 != 0 || d->a3 == nullptr || (d->c4 > 0 && d->a4 == nullptr) || d->upsample) return 0;
     if ((long)d->M * std::max(d->lda3 ? d->lda3 : d->c3, d->lda4 ? d->lda4 : d->c4) * 2 >= (1L << 32)) return 0;
+    if ((long)d->B * d->H * d->W >= (1L << 24)) return 0;        // the tail form's halo gather multiplies pixel indices with __umul24
   }
   const int up = d->upsample ? 2 : 1;                              // nearest x2 folded into the halo gather
   if ((d->stride ? d->stride : 1) != 1 || d->Ho != up * d->H || d->Wo != up * d->W) return 0;
   if (d->M % CH_BM != 0 || d->M != d->B * d->Ho * d->Wo) return 0;
   if (d->act == AF_ACT_GEGLU || d->out_mode == AF_OUT_SPLIT_T || d->ln_colsum != nullptr || d->kpad % 64 != 0) return 0;
   if ((long)d->B * d->H * d->W * std::max(d->c1, d->c2) * 2 >= (1L << 32)) return 0;      // the halo gather's 32-bit byte offsets
+  if ((long)((d->N + 127) / 128 * 128) * d->kpad * 2 >= (1L << 32)) return 0;                // ... and the weight pieces' (w_off)
   if (d->Wo > 64) {                                                // patches: no K tail, no split-K (the caller checks), no 160-wide form
     if (n160 || d->Wo % 16 != 0 || d->Ho % 16 != 0 || d->c3 || d->c4) return 0;
     return 3;
@@ -2275,6 +2277,7 @@ int af_gemm3_try_launch(const af_gemm_desc* d, int splits, int wide, hipStream_t
     // the whole-line kernel's loaders hold 32-bit byte offsets into the row-addressed operands (round 6): anything larger goes to the register-staged kernel
     const long ldmax = std::max(std::max((long)(d->lda1 ? d->lda1 : d->c1), (long)(d->lda2 ? d->lda2 : d->c2)), std::max((long)(d->lda3 ? d->lda3 : d->c3), (long)(d->lda4 ? d->lda4 : d->c4)));
     if (wide >= 4 && wide != 11 && (long)d->M * ldmax * 2 >= (1L << 32)) return 1;
+    if (wide >= 4 && wide != 11 && (long)p.npad * p.kpad * 2 >= (1L << 32)) return 1;     // ... and into the packed weight (w_off)
   }
   {
     const int ncols = geglu ? d->N / 2 : d->N;

@@ -181,6 +181,11 @@ def conv_halo_eligible(d) -> bool:
         return False
     if tail and not (n160 and d.c3 > 0 and d.c3 % 64 == 0 and d.c4 % 64 == 0 and not d.upsample):     # round 6: the K-concatenated 1x1 shortcut
         return False
+    # the kernel's 32-bit address arithmetic (conv3h_variant): the halo gather's byte offsets, the tail form's __umul24 pixel indices, the weight offsets
+    if d.B * d.H * d.W * max(d.c1, d.c2) * 2 >= 1 << 32 or (tail and d.B * d.H * d.W >= 1 << 24) or round_up(d.N, 128) * d.kpad * 2 >= 1 << 32:
+        return False
+    if tail and d.M * max(d.lda3 or d.c3, d.lda4 or d.c4) * 2 >= 1 << 32:
+        return False
     if d.Wo > 64:
         return not n160 and not tail and d.Wo % 16 == 0 and d.Ho % 16 == 0 and d.splits <= 1
     return d.Wo in (8, 16, 32, 64) and _halo_rows_ok(d.Ho, d.Wo)
