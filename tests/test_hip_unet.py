@@ -304,7 +304,6 @@ def test_unet_full_size_nonsquare_768x512_vs_oracle(dev, full_model):
     t = torch.tensor([321])
     with torch.no_grad():
         eps = full_model(x.to(dev), t.to(dev), ctx.to(dev), extra_info={})
-        torch.set_num_threads(min(32, os.cpu_count() or 8))
         ref = O.unet_forward(sd, SD15_UNET_CONFIG, x, t, ctx, {})
     err = rel_l2(eps.cpu().numpy(), ref.numpy())
     print(f"full-size 96x64 latent, 97 tokens: eps rel-L2 vs oracle {err:.3e}")
