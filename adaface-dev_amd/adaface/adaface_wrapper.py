@@ -19,10 +19,16 @@ files or VAE weights, so every component can be passed in, and:
 what ``adaface_translate.py`` runs): ``forward``'s first argument carries the input image(s) (one PIL image or a list of 1 or
 ``out_image_count``; see ``img2img_images_u8``), ``vae`` must be an ``AutoencoderKL`` (encoder + decoder), and ``ref_img_strength``
 picks how many of the last steps of the schedule run (``DDIMSampler.img2img_steps``).  The images are encoded once
-(``LatentDiffusion.img2img_latents``: two fused kernels around the VAE encoder) and denoised by ``DDIMSampler.sample_img2img``.
+(``LatentDiffusion.img2img_latents``: two fused kernels around the VAE encoder) and denoised by ``DDIMSampler.sample_img2img``
+(``DPMSolverSampler.sample_img2img`` under ``"dpm++"``).
 
-SDXL / SD3 / flux pipelines, LCM, other schedulers, inpainting, U-Net ensembles and the ConsistentID encoder are out of scope
-(external packages)."""
+``default_scheduler_name="dpm++"`` (the reference's DPM-Solver++ scheduler, diffusers' ``DPMSolverSinglestepScheduler`` with its
+defaults; INTEGRATION.md "DPM-Solver++ scheduler") samples both pipelines with ``DPMSolverSampler`` instead of ``DDIMSampler``: the same
+(cond, uncond) batches and guidance rule, one fused guidance + DPM-Solver++ update per step, typically at 20-25 ``num_inference_steps``
+rather than 50.  ``"ddim"`` stays the default.
+
+SDXL / SD3 / flux pipelines, LCM, schedulers other than DDIM and DPM-Solver++, inpainting, U-Net ensembles and the ConsistentID
+encoder are out of scope (external packages)."""
 import re
 import zlib
 
@@ -33,6 +39,7 @@ import torch.nn as nn
 from .. import SD15_UNET_CONFIG
 from ..ldm.models.diffusion.ddim import DDIMSampler
 from ..ldm.models.diffusion.ddpm import LatentDiffusion
+from ..ldm.models.diffusion.dpm_solver import DPMSolverSampler
 from .arc2face_models import CLIPTextModelWrapper, clip_text_config
 from .face_id_to_ada_prompt import Arc2Face_ID2AdaPrompt
 from .subj_basis_generator import CLIP_BOS, CLIP_EOS, CLIP_IDS
@@ -63,6 +70,10 @@ def img2img_images_u8(images, out_image_count):
             im = im.resize((w64, h64), resample=Image.LANCZOS)
         arrs.append(np.asarray(im, dtype=np.uint8))
     return torch.from_numpy(np.stack(arrs))
+
+
+# default_scheduler_name -> sampler class (both take the LatentDiffusion and offer sample / img2img_steps / sample_img2img)
+SCHEDULERS = {"ddim": DDIMSampler, "dpm++": DPMSolverSampler}
 
 
 class WordTokenizer:
@@ -127,9 +138,11 @@ class AdaFaceWrapper(nn.Module):
                                       "are built")
         if list(adaface_encoder_types) != ["arc2face"]:
             raise NotImplementedError("only the Arc2Face ID encoder is in scope (ConsistentID needs an external package)")
-        if use_lcm or default_scheduler_name != "ddim":
-            raise NotImplementedError("only the DDIM scheduler without LCM is built")
+        if use_lcm or default_scheduler_name not in SCHEDULERS:
+            raise NotImplementedError(f"scheduler {default_scheduler_name!r}{' with LCM' if use_lcm else ''}: only "
+                                      f"{' and '.join(map(repr, SCHEDULERS))} without LCM are built")
         self.pipeline_name = pipeline_name
+        self.default_scheduler_name = default_scheduler_name
         self.adaface_encoder_types = list(adaface_encoder_types)
         self.adaface_ckpt_paths = adaface_ckpt_paths
         self.enabled_encoders = enabled_encoders
@@ -315,7 +328,7 @@ class AdaFaceWrapper(nn.Module):
                 raise ValueError("the img2img pipeline encodes its input images: it needs an AutoencoderKL (encoder + decoder) as vae, "
                                  f"got {type(self.vae).__name__ if self.vae is not None else None}")
             images_u8 = img2img_images_u8(noise, out_image_count)
-            DDIMSampler(self.ldm).img2img_steps(self.num_inference_steps, ref_img_strength)    # refuse a bad strength before any work
+            self._sampler().img2img_steps(self.num_inference_steps, ref_img_strength)    # refuse a bad strength before any work
         if prompt_embeds is None:
             pe, ne, _, _ = self.encode_prompt(prompt, negative_prompt, placeholder_tokens_pos=placeholder_tokens_pos,
                                               ablate_prompt_only_placeholders=ablate_prompt_only_placeholders,
@@ -330,7 +343,7 @@ class AdaFaceWrapper(nn.Module):
         pe = pe.repeat(out_image_count, 1, 1)
         ne = None if ne is None else ne.repeat(out_image_count, 1, 1)
         self.ldm.to(self.device)
-        sampler = DDIMSampler(self.ldm)
+        sampler = self._sampler()
         cond = (pe, [prompt or ""] * out_image_count, {})
         uncond = None if ne is None else (ne, [negative_prompt or self.negative_prompt] * out_image_count, {})
         if self.pipeline_name == "img2img":
@@ -346,6 +359,9 @@ class AdaFaceWrapper(nn.Module):
         if self.vae is None:
             return latents
         return self._to_pil(latents)
+
+    def _sampler(self):
+        return SCHEDULERS[self.default_scheduler_name](self.ldm)
 
     def _to_pil(self, latents):
         images = self.vae.decode(latents / 0.18215)

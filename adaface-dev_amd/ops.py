@@ -938,6 +938,24 @@ def cfg_ddim_step(eps2: torch.Tensor, x: torch.Tensor, guidance: float, a_t: flo
     return x_prev, pred_x0
 
 
+def cfg_dpmpp_step(eps2: torch.Tensor, x: torch.Tensor, x_base: torch.Tensor, x0_prev: Optional[torch.Tensor], guidance: float,
+                   alpha_s: float, sigma_s: float, c_base: float, c0: float, c1: float, has_uncond: bool = True):
+    """eps2 fp32 [2n or n] = [e_cond ; e_uncond], x / x_base / x0_prev fp32 [n] -> (x_out, x0_out): one DPM-Solver++ step,
+    x0 = (x - sigma_s e) / alpha_s, x_out = c_base x_base + c0 x0 + c1 x0_prev (x0_prev unused, may be None, when c1 == 0)."""
+    assert eps2.dtype == torch.float32 and x.dtype == torch.float32 and eps2.is_contiguous() and x.is_contiguous()
+    n = x.numel()
+    assert eps2.numel() == (2 * n if has_uncond else n)
+    assert x_base.dtype == torch.float32 and x_base.is_contiguous() and x_base.numel() == n
+    if c1 != 0.0:
+        assert x0_prev is not None and x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == n
+    x_out, x0_out = torch.empty_like(x), torch.empty_like(x)
+    prev = _p(x0_prev) if c1 != 0.0 else None
+    _lib.check(_lib.lib().af_cfg_dpmpp_step(_p(eps2), _p(x), _p(x_base), prev, _p(x_out), _p(x0_out), n, int(has_uncond),
+                                            float(guidance), float(alpha_s), float(sigma_s), float(c_base), float(c0), float(c1),
+                                            _stream()), "af_cfg_dpmpp_step")
+    return x_out, x0_out
+
+
 def q_sample(x0: torch.Tensor, noise: torch.Tensor, sa: torch.Tensor, sb: torch.Tensor) -> torch.Tensor:
     """x_t = sa[b] x0 + sb[b] noise (ddpm.py:395-398); fp32."""
     x0, noise = x0.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous()

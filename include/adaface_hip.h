@@ -371,6 +371,12 @@ int af_nhwc_f16_to_nchw_f32(const void* x, void* y, int B, int C, int HW, int cs
  * e_u == NULL (n_uncond = 0) means no guidance.  x, x_prev, pred_x0: fp32 [n].              */
 int af_cfg_ddim_step(const void* eps2, const void* x, void* x_prev, void* pred_x0, int64_t n, int has_uncond,
                      float guidance, float a_t, float a_prev, void* stream);
+/* classifier-free guidance + one DPM-Solver++ step (2S, midpoint; INTEGRATION.md "DPM-Solver++ scheduler") in data-prediction form:
+ * e = e_u + g (e_c - e_u) (e = e_c when has_uncond == 0); x0 = (x - sigma_s e) / alpha_s;
+ * x0_out = x0; x_out = c_base x_base + c0 x0 + c1 x0_prev, all fp32 [n].  eps2 = [e_c ; e_u] fp32 [2n] (or [n]).
+ * x0_prev is not read when c1 == 0 and may then be NULL.  alpha_s in (0, 1], sigma_s in [0, 1), coefficients finite.        */
+int af_cfg_dpmpp_step(const void* eps2, const void* x, const void* x_base, const void* x0_prev, void* x_out, void* x0_out, int64_t n,
+                      int has_uncond, float guidance, float alpha_s, float sigma_s, float c_base, float c0, float c1, void* stream);
 /* q_sample (ldm/models/diffusion/ddpm.py:395-398): x_t = sa[b] x0 + sb[b] noise, fp32, per-sample scalars */
 int af_q_sample(const void* x0, const void* noise, const void* sa, const void* sb, void* xt, int B, int64_t per,
                 void* stream);

@@ -2,7 +2,7 @@
 """The img2img pipeline end to end at full size through the AdaFaceWrapper surface (seeded random weights): one 512 x 512 input image
 -> uint8 upload -> VAE encoder + fused quant_conv / posterior / q_sample -> the last 40 of 50 DDIM steps (strength 0.8) with CFG on the
 SD-1.5 U-Net (batch 4 + 4) -> VAE decoder -> 4 PIL images.  Prints the time of each phase after one warm-up pass (eager launches).
-                                                                                        python tools/e2e_img2img.py [steps] [strength]"""
+                                                          python tools/e2e_img2img.py [steps] [strength] [scheduler: ddim | dpm++]"""
 import os
 import sys
 import time
@@ -18,13 +18,13 @@ def main():
 
     from adaface_dev_amd import rng
     from adaface_dev_amd.adaface.adaface_wrapper import AdaFaceWrapper, img2img_images_u8
-    from adaface_dev_amd.ldm.models.diffusion.ddim import DDIMSampler
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     strength = float(sys.argv[2]) if len(sys.argv) > 2 else 0.8
+    scheduler = sys.argv[3] if len(sys.argv) > 3 else "ddim"
     count = 4
     dev = torch.device("cuda:0")
     t0 = time.perf_counter()
-    w = AdaFaceWrapper(pipeline_name="img2img", device=dev, num_inference_steps=steps)
+    w = AdaFaceWrapper(pipeline_name="img2img", device=dev, num_inference_steps=steps, default_scheduler_name=scheduler)
     rng.load_synth_weights(w.ldm.model.diffusion_model, seed=0)
     vae = w.ldm.instantiate_first_stage()
     with torch.no_grad():
@@ -48,7 +48,7 @@ def main():
     ne = rng.synth_input("e2e.ne", (1, 77, 768), seed=8).to(dev)
     cond = (pe.repeat(count, 1, 1), [""] * count, {})
     uncond = (ne.repeat(count, 1, 1), [""] * count, {})
-    sampler = DDIMSampler(w.ldm)
+    sampler = w._sampler()
     n, t_first = sampler.img2img_steps(steps, strength)
     for it in range(2):                                      # first pass packs weights / warms kernels
         x_t, t_enc = timed(lambda: w.ldm.img2img_latents(img2img_images_u8(img, count).to(dev), count, t_first,
@@ -59,7 +59,7 @@ def main():
     imgs, t_all = timed(lambda: w(img, None, prompt_embeds=(pe, ne), guidance_scale=6.0, out_image_count=count, ref_img_strength=strength,
                                   generator=torch.Generator().manual_seed(1)))
     print(f"build+weights {t_build:.1f} s | image upload + VAE encode + latents (1 image 512x512) {t_enc * 1e3:.1f} ms | "
-          f"{n} of {steps} DDIM steps (strength {strength}, t_first {t_first}, U-Net batch {2 * count}, eager) {t_ddim * 1e3:.1f} ms = "
+          f"{n} of {steps} {scheduler} steps (strength {strength}, t_first {t_first}, U-Net batch {2 * count}, eager) {t_ddim * 1e3:.1f} ms = "
           f"{t_ddim / n * 1e3:.2f} ms/step | VAE decode x{count} {t_vae * 1e3:.1f} ms | whole img2img forward() incl. PIL {t_all * 1e3:.1f} ms | "
           f"{len(imgs)} images {imgs[0].size}, latents finite={bool(torch.isfinite(lat).all())}")
 

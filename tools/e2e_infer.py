@@ -2,7 +2,7 @@
 """BASELINE configs[1] end to end at full size through the AdaFaceWrapper surface (seeded random weights): face IDs -> Arc2Face
 image prompt -> AdaFace token embeddings -> token table -> rewritten prompt -> CLIP-L text encoder -> 50 DDIM steps with CFG on the
 SD-1.5 U-Net (batch 4 + 4) -> VAE decoder -> 4 PIL images.  Prints the time of each phase (eager launches; bench.py measures the
-denoise step under hipGraph replay).      python tools/e2e_infer.py [steps]"""
+denoise step under hipGraph replay).      python tools/e2e_infer.py [steps] [scheduler: ddim (default) | dpm++]"""
 import os
 import sys
 import time
@@ -17,9 +17,10 @@ def main():
     from adaface_dev_amd.adaface.adaface_wrapper import AdaFaceWrapper
     from adaface_dev_amd.ldm.modules.diffusionmodules.model import AutoencoderKLDecoder
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+    scheduler = sys.argv[2] if len(sys.argv) > 2 else "ddim"
     dev = torch.device("cuda:0")
     t0 = time.perf_counter()
-    w = AdaFaceWrapper(device=dev, num_inference_steps=steps)
+    w = AdaFaceWrapper(device=dev, num_inference_steps=steps, default_scheduler_name=scheduler)
     rng.load_synth_weights(w.text_encoder, seed=60)
     rng.load_synth_weights(w.id2ada_prompt_encoder.text_to_image_prompt_encoder, seed=61)
     rng.load_synth_weights(w.id2ada_prompt_encoder.subj_basis_generator.prompt2token_proj, seed=62)
@@ -54,7 +55,7 @@ def main():
     w.vae = vae
     imgs, t_all = timed(lambda: w(noise, prompt, guidance_scale=6.0, out_image_count=4))
     print(f"build+weights {t_build:.1f} s | AdaFace embeddings {t_emb * 1e3:.1f} ms | prompt encode (pos+neg) {t_enc * 1e3:.1f} ms | "
-          f"{steps} DDIM steps (U-Net batch 8, eager) {t_ddim * 1e3:.1f} ms = {t_ddim / steps * 1e3:.2f} ms/step | VAE decode x4 {t_vae * 1e3:.1f} ms | "
+          f"{steps} {scheduler} steps (U-Net batch 8, eager) {t_ddim * 1e3:.1f} ms = {t_ddim / steps * 1e3:.2f} ms/step | VAE decode x4 {t_vae * 1e3:.1f} ms | "
           f"whole forward() incl. PIL {t_all * 1e3:.1f} ms | {len(imgs)} images {imgs[0].size}, latents finite={bool(torch.isfinite(lat).all())}, "
           f"embs {tuple(embs.shape)}")
 
