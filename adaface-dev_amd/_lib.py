@@ -33,7 +33,7 @@ EXPORTS = (
     "af_softmax_rows_bwd", "af_affine_prelu_bwd", "af_maxpool2x2_bwd", "af_se_gate_grad", "af_se_residual_prelu_bwd",
     "af_groupnorm_apply", "af_gemm_gn_stats_ok", "af_gemm_halo_variant", "af_gn_proj_fused",
     "af_splitk_reduce", "af_groupnorm_splitk_ok", "af_groupnorm_splitk", "af_xattn_chain",
-    "af_image_u8_to_nhwc_f16", "af_vae_latents_q_sample", "af_cfg_dpmpp_step",
+    "af_image_u8_to_nhwc_f16", "af_vae_latents_q_sample", "af_cfg_dpmpp_step", "af_cfg_lcm_step",
 )
 
 
@@ -141,6 +141,7 @@ def lib() -> C.CDLL:
     L.af_nhwc_f16_to_nchw_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.af_cfg_ddim_step.argtypes = [vp, vp, vp, vp, i64, i32, f32, f32, f32, vp]
     L.af_cfg_dpmpp_step.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, f32, vp]
+    L.af_cfg_lcm_step.argtypes = [vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, f32, f32, vp]
     L.af_q_sample.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp]
     L.af_image_u8_to_nhwc_f16.argtypes = [vp, vp, i32, i32, i32, vp]
     L.af_vae_latents_q_sample.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, vp, i32, i32, i32, i32, vp]

@@ -27,8 +27,15 @@ defaults; INTEGRATION.md "DPM-Solver++ scheduler") samples both pipelines with `
 (cond, uncond) batches and guidance rule, one fused guidance + DPM-Solver++ update per step, typically at 20-25 ``num_inference_steps``
 rather than 50.  ``"ddim"`` stays the default.
 
-SDXL / SD3 / flux pipelines, LCM, schedulers other than DDIM and DPM-Solver++, inpainting, U-Net ensembles and the ConsistentID
-encoder are out of scope (external packages)."""
+``use_lcm=True, lcm_lora_path=...`` (the reference's LCM-LoRA mode; INTEGRATION.md "LCM-LoRA") fuses an SD-1.5 U-Net LoRA such as
+LCM-LoRA into the U-Net weights once (``adaface/sd_lora.py``; after ``base_model_path`` is loaded, again after every later
+``load_base_model``) and samples both pipelines with ``LCMSampler``, typically at 4 ``num_inference_steps``: the guidance scale is
+constant, the (cond, uncond) batch runs only when the scale is above 1, and ``forward``'s ``generator`` draws the re-noising of every
+step but the last.  Nothing is downloaded: ``lcm_lora_path`` is a local file or an in-memory state dict.  ``fuse_lcm_lora`` /
+``unfuse_lcm_lora`` change the weights only; the sampler follows ``use_lcm``.
+
+SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, inpainting, U-Net ensembles and
+the ConsistentID encoder are out of scope (external packages)."""
 import re
 import zlib
 
@@ -40,6 +47,8 @@ from .. import SD15_UNET_CONFIG
 from ..ldm.models.diffusion.ddim import DDIMSampler
 from ..ldm.models.diffusion.ddpm import LatentDiffusion
 from ..ldm.models.diffusion.dpm_solver import DPMSolverSampler
+from ..ldm.models.diffusion.lcm import LCMSampler, lcm_timesteps
+from . import sd_lora
 from .arc2face_models import CLIPTextModelWrapper, clip_text_config
 from .face_id_to_ada_prompt import Arc2Face_ID2AdaPrompt
 from .subj_basis_generator import CLIP_BOS, CLIP_EOS, CLIP_IDS
@@ -74,6 +83,11 @@ def img2img_images_u8(images, out_image_count):
 
 # default_scheduler_name -> sampler class (both take the LatentDiffusion and offer sample / img2img_steps / sample_img2img)
 SCHEDULERS = {"ddim": DDIMSampler, "dpm++": DPMSolverSampler}
+
+
+class LCMLoRAMissing(ValueError, NotImplementedError):
+    """``use_lcm=True`` without ``lcm_lora_path``.  A ValueError; also a NotImplementedError, which is what ``use_lcm=True`` raised
+    before LCM sampling was built, so callers that caught that keep working."""
 
 
 class WordTokenizer:
@@ -131,17 +145,28 @@ class AdaFaceWrapper(nn.Module):
                  adaface_encoder_cfg_scales=None, enabled_encoders=None, use_lcm=False, default_scheduler_name="ddim",
                  num_inference_steps=50, subject_string="z", negative_prompt=None, max_prompt_length=77,
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
-                 tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None):
+                 tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
+                 lcm_lora_path=None, lcm_lora_scale=1.0):
         super().__init__()
         if pipeline_name not in ("text2img", "img2img", None):
             raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img and img2img paths (and None = face encoder only) "
                                       "are built")
         if list(adaface_encoder_types) != ["arc2face"]:
             raise NotImplementedError("only the Arc2Face ID encoder is in scope (ConsistentID needs an external package)")
-        if use_lcm or default_scheduler_name not in SCHEDULERS:
-            raise NotImplementedError(f"scheduler {default_scheduler_name!r}{' with LCM' if use_lcm else ''}: only "
-                                      f"{' and '.join(map(repr, SCHEDULERS))} without LCM are built")
+        if default_scheduler_name not in SCHEDULERS:
+            raise NotImplementedError(f"scheduler {default_scheduler_name!r}: only {' and '.join(map(repr, SCHEDULERS))} (and "
+                                      "use_lcm=True) are built")
+        if use_lcm:
+            if pipeline_name is None:
+                raise ValueError("use_lcm=True needs a pipeline: pipeline_name=None builds the face encoder only")
+            if lcm_lora_path is None:
+                raise LCMLoRAMissing("use_lcm=True needs lcm_lora_path (a local LCM-LoRA file such as the pytorch_lora_weights.safetensors "
+                                     "of latent-consistency/lcm-lora-sdv1-5, or its state dict): nothing is downloaded")
+            lcm_timesteps(num_inference_steps)          # 1 .. 50 steps, else ValueError
+        elif lcm_lora_path is not None:
+            raise ValueError("lcm_lora_path is given but use_lcm is False")
         self.pipeline_name = pipeline_name
+        self.use_lcm = use_lcm
         self.default_scheduler_name = default_scheduler_name
         self.adaface_encoder_types = list(adaface_encoder_types)
         self.adaface_ckpt_paths = adaface_ckpt_paths
@@ -167,8 +192,12 @@ class AdaFaceWrapper(nn.Module):
         self.ldm = None if pipeline_name is None else (ldm or LatentDiffusion(unet_config or SD15_UNET_CONFIG))
         self.vae = vae
         self.img_prompt_embs = None
+        self._lcm_lora = None                 # (read_unet_lora dict, scale) of the fused LoRA
+        self._lcm_saved = {}                  # {ldm_path: original weight} while it is fused
         if base_model_path is not None:
             self.load_base_model(base_model_path)
+        if use_lcm:
+            self.fuse_lcm_lora(lcm_lora_path, lcm_lora_scale)
         self.extend_tokenizer_and_text_encoder()
         if adaface_ckpt_paths:
             self.load_subj_basis_generator(adaface_ckpt_paths)
@@ -185,10 +214,37 @@ class AdaFaceWrapper(nn.Module):
         if self.ldm.cond_stage_model is None:       # share the wrapper's text encoder so that the checkpoint's CLIP weights reach it
             self.ldm.instantiate_cond_stage(FrozenCLIPEmbedder(tokenizer=self.tokenizer, transformer=self.text_encoder,
                                                                last_layers_skip_weights=None))
+        if self._lcm_saved:                   # the checkpoint goes into the unfused weights, the LoRA is fused again onto it
+            sd_lora.unfuse_unet_lora(self.ldm.model, self._lcm_saved)
+            self._lcm_saved = {}
         missing, unexpected = self.ldm.init_from_ckpt(base_model_path)
         if self.vae is None:
             self.vae = self.ldm.first_stage_model
+        if self._lcm_lora is not None:
+            self._lcm_saved = sd_lora.fuse_unet_lora(self.ldm.model, *self._lcm_lora)
         return missing, unexpected
+
+    def fuse_lcm_lora(self, path_or_state_dict, scale=1.0):
+        """Fuse an SD-1.5 U-Net LoRA (a .safetensors / .bin / .pt file or a state dict in the kohya, diffusers or peft layout;
+        adaface/sd_lora.py) into the U-Net weights: W' = W + scale * (alpha / r) * up @ down.  A LoRA fused earlier is unfused first.
+        Raises RuntimeError while an AdaFace DoRA adapter merge is live.  Do not replay a graph captured before the fuse."""
+        if self.ldm is None:
+            raise RuntimeError("pipeline_name=None builds the face encoder only: there is no U-Net to fuse a LoRA into")
+        sd_lora.check_no_live_merge(self.ldm.model)
+        lora = sd_lora.read_unet_lora(path_or_state_dict, self.ldm.model)
+        self.unfuse_lcm_lora()
+        self._lcm_saved = sd_lora.fuse_unet_lora(self.ldm.model, lora, scale)
+        self._lcm_lora = (lora, scale)
+
+    def unfuse_lcm_lora(self):
+        """Restore the U-Net weights saved by fuse_lcm_lora, bit-exactly (nothing to do when no LoRA is fused).  Raises RuntimeError
+        while an AdaFace DoRA adapter merge is live."""
+        if self.ldm is not None:
+            sd_lora.check_no_live_merge(self.ldm.model)
+        if self._lcm_saved:
+            sd_lora.unfuse_unet_lora(self.ldm.model, self._lcm_saved)
+        self._lcm_saved = {}
+        self._lcm_lora = None
 
     def load_subj_basis_generator(self, adaface_ckpt_paths):
         """``embeddings_gs-N.pt`` as written by ``EmbeddingManager.save`` (pickled generator modules; the reference's class paths
@@ -344,6 +400,7 @@ class AdaFaceWrapper(nn.Module):
         ne = None if ne is None else ne.repeat(out_image_count, 1, 1)
         self.ldm.to(self.device)
         sampler = self._sampler()
+        lcm_kw = {"generator": generator} if self.use_lcm else {}
         cond = (pe, [prompt or ""] * out_image_count, {})
         uncond = None if ne is None else (ne, [negative_prompt or self.negative_prompt] * out_image_count, {})
         if self.pipeline_name == "img2img":
@@ -351,17 +408,17 @@ class AdaFaceWrapper(nn.Module):
             x_t = self.ldm.img2img_latents(images_u8.to(self.device), out_image_count, t_first, generator=generator,
                                            first_stage_model=self.vae)
             latents, _ = sampler.sample_img2img(self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond,
-                                                guidance_scale=guidance_scale, unconditional_conditioning=uncond)
+                                                guidance_scale=guidance_scale, unconditional_conditioning=uncond, **lcm_kw)
             return self._to_pil(latents)
         noise = noise.to(device=self.device, dtype=torch.float32)
         latents, _ = sampler.sample(self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise,
-                                    verbose=False, guidance_scale=guidance_scale, unconditional_conditioning=uncond)
+                                    verbose=False, guidance_scale=guidance_scale, unconditional_conditioning=uncond, **lcm_kw)
         if self.vae is None:
             return latents
         return self._to_pil(latents)
 
     def _sampler(self):
-        return SCHEDULERS[self.default_scheduler_name](self.ldm)
+        return LCMSampler(self.ldm) if self.use_lcm else SCHEDULERS[self.default_scheduler_name](self.ldm)
 
     def _to_pil(self, latents):
         images = self.vae.decode(latents / 0.18215)

@@ -166,6 +166,51 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const float* __restrict_
   }
 }
 
+// classifier-free guidance + one LCM (multistep consistency) step, per element:
+// e = e_u + g (e_c - e_u); x0 = (x - sqrt(1 - abar_t) e) / sqrt(abar_t); d = c_out x0 + c_skip x;
+// x_next = sqrt(abar_next) d + sqrt(1 - abar_next) noise, or d on the last step (HAS_NOISE = false never touches noise).
+// V4: 16-byte accesses, n % 4 == 0, all pointers aligned.
+struct LcmCoefs {
+  float g, sa, sb, c_out, c_skip, sa_next, sb_next;
+};
+
+template <bool HAS_NOISE>
+__device__ __forceinline__ float lcm_elem(float ec, float eu, int has_uncond, float x, float nz, const LcmCoefs& k, float& d) {
+  const float e = has_uncond ? eu + k.g * (ec - eu) : ec;
+  const float x0 = (x - k.sb * e) / k.sa;
+  d = k.c_out * x0 + k.c_skip * x;
+  return HAS_NOISE ? k.sa_next * d + k.sb_next * nz : d;
+}
+
+template <bool HAS_NOISE, bool V4>
+__global__ __launch_bounds__(256) void cfg_lcm_kernel(const float* __restrict__ eps2, const float* __restrict__ x,
+                                                      const float* __restrict__ noise, float* __restrict__ x_next,
+                                                      float* __restrict__ denoised, long n, int has_uncond, LcmCoefs k) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (V4) {
+    if (i >= n / 4) return;
+    const float4 ec = reinterpret_cast<const float4*>(eps2)[i];
+    const float4 eu = has_uncond ? reinterpret_cast<const float4*>(eps2 + n)[i] : ec;
+    const float4 xv = reinterpret_cast<const float4*>(x)[i];
+    const float4 nz = HAS_NOISE ? reinterpret_cast<const float4*>(noise)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 y, d;
+    y.x = lcm_elem<HAS_NOISE>(ec.x, eu.x, has_uncond, xv.x, nz.x, k, d.x);
+    y.y = lcm_elem<HAS_NOISE>(ec.y, eu.y, has_uncond, xv.y, nz.y, k, d.y);
+    y.z = lcm_elem<HAS_NOISE>(ec.z, eu.z, has_uncond, xv.z, nz.z, k, d.z);
+    y.w = lcm_elem<HAS_NOISE>(ec.w, eu.w, has_uncond, xv.w, nz.w, k, d.w);
+    reinterpret_cast<float4*>(denoised)[i] = d;
+    reinterpret_cast<float4*>(x_next)[i] = y;
+  } else {
+    if (i >= n) return;
+    const float ec = eps2[i];
+    const float eu = has_uncond ? eps2[n + i] : ec;
+    float d;
+    const float y = lcm_elem<HAS_NOISE>(ec, eu, has_uncond, x[i], HAS_NOISE ? noise[i] : 0.f, k, d);
+    denoised[i] = d;
+    x_next[i] = y;
+  }
+}
+
 __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise, const float* __restrict__ sa,
                                 const float* __restrict__ sb, float* __restrict__ xt, int B, long per) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -303,6 +348,37 @@ extern "C" int af_cfg_dpmpp_step(const void* eps2, const void* x, const void* x_
   else
     hipLaunchKernelGGL((cfg_dpmpp_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, xb, xp, xo, x0o, (long)n, has_uncond, k);
   return af_check_launch("af_cfg_dpmpp_step");
+}
+
+extern "C" int af_cfg_lcm_step(const void* eps2, const void* x, const void* noise, void* x_next, void* denoised, int64_t n,
+                               int has_uncond, float guidance, float sqrt_a, float sqrt_1ma, float c_out, float c_skip,
+                               float sqrt_a_next, float sqrt_1ma_next, void* stream) {
+  AF_REQUIRE(eps2 && x && x_next && denoised && n > 0, "af_cfg_lcm_step: bad argument");
+  AF_REQUIRE(sqrt_a > 0.f && sqrt_a <= 1.f && sqrt_1ma >= 0.f && sqrt_1ma < 1.f,
+             "af_cfg_lcm_step: need sqrt_a in (0, 1] and sqrt_1ma in [0, 1)");
+  AF_REQUIRE(std::isfinite(guidance) && std::isfinite(c_out) && std::isfinite(c_skip) && std::isfinite(sqrt_a_next) &&
+                 std::isfinite(sqrt_1ma_next),
+             "af_cfg_lcm_step: coefficients must be finite");
+  const bool has_noise = noise != nullptr;
+  AF_REQUIRE(!has_noise || (sqrt_a_next > 0.f && sqrt_a_next <= 1.f && sqrt_1ma_next >= 0.f && sqrt_1ma_next < 1.f),
+             "af_cfg_lcm_step: need sqrt_a_next in (0, 1] and sqrt_1ma_next in [0, 1)");
+  const LcmCoefs k{guidance, sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next, sqrt_1ma_next};
+  const uintptr_t align = reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_next) |
+                          reinterpret_cast<uintptr_t>(denoised) | (has_noise ? reinterpret_cast<uintptr_t>(noise) : 0);
+  const bool v4 = n % 4 == 0 && (align & 15) == 0;
+  const dim3 grid = grid1d(v4 ? n / 4 : n);
+  const auto *e = (const float*)eps2, *xx = (const float*)x, *nz = (const float*)noise;
+  auto *xn = (float*)x_next, *dn = (float*)denoised;
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  if (has_noise && v4)
+    hipLaunchKernelGGL((cfg_lcm_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, nz, xn, dn, (long)n, has_uncond, k);
+  else if (has_noise)
+    hipLaunchKernelGGL((cfg_lcm_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, nz, xn, dn, (long)n, has_uncond, k);
+  else if (v4)
+    hipLaunchKernelGGL((cfg_lcm_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, nz, xn, dn, (long)n, has_uncond, k);
+  else
+    hipLaunchKernelGGL((cfg_lcm_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, nz, xn, dn, (long)n, has_uncond, k);
+  return af_check_launch("af_cfg_lcm_step");
 }
 
 extern "C" int af_q_sample(const void* x0, const void* noise, const void* sa, const void* sb, void* xt, int B, int64_t per,

@@ -956,6 +956,23 @@ def cfg_dpmpp_step(eps2: torch.Tensor, x: torch.Tensor, x_base: torch.Tensor, x0
     return x_out, x0_out
 
 
+def cfg_lcm_step(eps2: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tensor], guidance: float, sqrt_a: float, sqrt_1ma: float,
+                 c_out: float, c_skip: float, sqrt_a_next: float = 0.0, sqrt_1ma_next: float = 0.0, has_uncond: bool = True):
+    """eps2 fp32 [2n or n] = [e_cond ; e_uncond], x / noise fp32 [n] -> (x_next, denoised): one LCM step,
+    x0 = (x - sqrt_1ma e) / sqrt_a, denoised = c_out x0 + c_skip x, x_next = sqrt_a_next denoised + sqrt_1ma_next noise
+    (noise None: the last step, x_next = denoised)."""
+    assert eps2.dtype == torch.float32 and x.dtype == torch.float32 and eps2.is_contiguous() and x.is_contiguous()
+    n = x.numel()
+    assert eps2.numel() == (2 * n if has_uncond else n)
+    if noise is not None:
+        assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == n
+    x_next, denoised = torch.empty_like(x), torch.empty_like(x)
+    _lib.check(_lib.lib().af_cfg_lcm_step(_p(eps2), _p(x), None if noise is None else _p(noise), _p(x_next), _p(denoised), n,
+                                          int(has_uncond), float(guidance), float(sqrt_a), float(sqrt_1ma), float(c_out), float(c_skip),
+                                          float(sqrt_a_next), float(sqrt_1ma_next), _stream()), "af_cfg_lcm_step")
+    return x_next, denoised
+
+
 def q_sample(x0: torch.Tensor, noise: torch.Tensor, sa: torch.Tensor, sb: torch.Tensor) -> torch.Tensor:
     """x_t = sa[b] x0 + sb[b] noise (ddpm.py:395-398); fp32."""
     x0, noise = x0.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous()

@@ -377,6 +377,14 @@ int af_cfg_ddim_step(const void* eps2, const void* x, void* x_prev, void* pred_x
  * x0_prev is not read when c1 == 0 and may then be NULL.  alpha_s in (0, 1], sigma_s in [0, 1), coefficients finite.        */
 int af_cfg_dpmpp_step(const void* eps2, const void* x, const void* x_base, const void* x0_prev, void* x_out, void* x0_out, int64_t n,
                       int has_uncond, float guidance, float alpha_s, float sigma_s, float c_base, float c0, float c1, void* stream);
+/* classifier-free guidance + one LCM step (multistep consistency sampling; INTEGRATION.md "LCM-LoRA"):
+ * e = e_u + g (e_c - e_u) (e = e_c when has_uncond == 0); x0 = (x - sqrt_1ma e) / sqrt_a; denoised = c_out x0 + c_skip x;
+ * x_next = sqrt_a_next denoised + sqrt_1ma_next noise, all fp32 [n].  eps2 = [e_c ; e_u] fp32 [2n] (or [n]).
+ * noise == NULL is the last step: x_next = denoised, noise is not read.  sqrt_a (and, with noise, sqrt_a_next) in (0, 1],
+ * sqrt_1ma (sqrt_1ma_next) in [0, 1), coefficients finite.                                                                  */
+int af_cfg_lcm_step(const void* eps2, const void* x, const void* noise, void* x_next, void* denoised, int64_t n, int has_uncond,
+                    float guidance, float sqrt_a, float sqrt_1ma, float c_out, float c_skip, float sqrt_a_next, float sqrt_1ma_next,
+                    void* stream);
 /* q_sample (ldm/models/diffusion/ddpm.py:395-398): x_t = sa[b] x0 + sb[b] noise, fp32, per-sample scalars */
 int af_q_sample(const void* x0, const void* noise, const void* sa, const void* sb, void* xt, int B, int64_t per,
                 void* stream);
