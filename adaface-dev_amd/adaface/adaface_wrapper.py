@@ -81,7 +81,7 @@ def img2img_images_u8(images, out_image_count):
     return torch.from_numpy(np.stack(arrs))
 
 
-# default_scheduler_name -> sampler class (both take the LatentDiffusion and offer sample / img2img_steps / sample_img2img)
+# default_scheduler_name -> sampler class (a sampling.Sampler, as LCMSampler: sample / img2img_steps / sample_img2img)
 SCHEDULERS = {"ddim": DDIMSampler, "dpm++": DPMSolverSampler}
 
 
@@ -400,7 +400,6 @@ class AdaFaceWrapper(nn.Module):
         ne = None if ne is None else ne.repeat(out_image_count, 1, 1)
         self.ldm.to(self.device)
         sampler = self._sampler()
-        lcm_kw = {"generator": generator} if self.use_lcm else {}
         cond = (pe, [prompt or ""] * out_image_count, {})
         uncond = None if ne is None else (ne, [negative_prompt or self.negative_prompt] * out_image_count, {})
         if self.pipeline_name == "img2img":
@@ -408,11 +407,11 @@ class AdaFaceWrapper(nn.Module):
             x_t = self.ldm.img2img_latents(images_u8.to(self.device), out_image_count, t_first, generator=generator,
                                            first_stage_model=self.vae)
             latents, _ = sampler.sample_img2img(self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond,
-                                                guidance_scale=guidance_scale, unconditional_conditioning=uncond, **lcm_kw)
+                                                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
             return self._to_pil(latents)
         noise = noise.to(device=self.device, dtype=torch.float32)
         latents, _ = sampler.sample(self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise,
-                                    verbose=False, guidance_scale=guidance_scale, unconditional_conditioning=uncond, **lcm_kw)
+                                    verbose=False, guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
         if self.vae is None:
             return latents
         return self._to_pil(latents)

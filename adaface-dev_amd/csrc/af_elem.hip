@@ -1,5 +1,8 @@
 // af_elem.hip -- small element-wise kernels around the U-Net: timestep embedding, layout
-// conversion at the NCHW fp32 API boundary, classifier-free guidance + DDIM / DPM-Solver++ update, q_sample.
+// conversion at the NCHW fp32 API boundary, classifier-free guidance + DDIM / DPM-Solver++ / LCM update, q_sample.
+#include <initializer_list>
+#include <type_traits>
+
 #include "af_common.h"
 
 namespace {
@@ -277,6 +280,25 @@ __global__ void silu_kernel(const half_t* __restrict__ x, half_t* __restrict__ y
 
 inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
+// The launch of a fused sampler step KERNEL<FLAG, V4> over n fp32 elements: V4 (one thread per float4) when n % 4 == 0 and every
+// pointer in `ptrs` is 16-byte aligned (NULL for one the FLAG = false form never touches), else one thread per element.
+// `launch(flag, v4, grid)` gets FLAG and V4 as std::bool_constant, to instantiate the kernel with.
+template <typename Launch>
+void launch_flag_v4(bool flag, long n, std::initializer_list<const void*> ptrs, Launch launch) {
+  uintptr_t align = 0;
+  for (const void* p : ptrs) align |= reinterpret_cast<uintptr_t>(p);
+  const bool v4 = n % 4 == 0 && (align & 15) == 0;
+  const dim3 grid = grid1d(v4 ? n / 4 : n);
+  if (flag && v4)
+    launch(std::true_type{}, std::true_type{}, grid);
+  else if (flag)
+    launch(std::true_type{}, std::false_type{}, grid);
+  else if (v4)
+    launch(std::false_type{}, std::true_type{}, grid);
+  else
+    launch(std::false_type{}, std::false_type{}, grid);
+}
+
 }  // namespace
 
 extern "C" int af_timestep_embedding(const void* timesteps_i64, void* out, int B, int dim, float max_period, void* stream) {
@@ -330,23 +352,11 @@ extern "C" int af_cfg_dpmpp_step(const void* eps2, const void* x, const void* x_
   const bool has_prev = c1 != 0.f;
   AF_REQUIRE(x0_prev || !has_prev, "af_cfg_dpmpp_step: x0_prev is NULL but c1 != 0");
   const DpmppCoefs k{guidance, sigma_s, alpha_s, c_base, c0, c1};
-  const uintptr_t align = reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_base) |
-                          reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(x0_out) |
-                          (has_prev ? reinterpret_cast<uintptr_t>(x0_prev) : 0);
-  const bool v4 = n % 4 == 0 && (align & 15) == 0;
-  const dim3 grid = grid1d(v4 ? n / 4 : n);
-  const auto* e = (const float*)eps2;
-  const auto *xx = (const float*)x, *xb = (const float*)x_base, *xp = (const float*)x0_prev;
-  auto *xo = (float*)x_out, *x0o = (float*)x0_out;
   AfLaunchScope scope(AF_FAM_ELEM, stream);
-  if (has_prev && v4)
-    hipLaunchKernelGGL((cfg_dpmpp_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, xb, xp, xo, x0o, (long)n, has_uncond, k);
-  else if (has_prev)
-    hipLaunchKernelGGL((cfg_dpmpp_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, xb, xp, xo, x0o, (long)n, has_uncond, k);
-  else if (v4)
-    hipLaunchKernelGGL((cfg_dpmpp_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, xb, xp, xo, x0o, (long)n, has_uncond, k);
-  else
-    hipLaunchKernelGGL((cfg_dpmpp_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, xb, xp, xo, x0o, (long)n, has_uncond, k);
+  launch_flag_v4(has_prev, n, {eps2, x, x_base, x_out, x0_out, has_prev ? x0_prev : nullptr}, [&](auto prev, auto v4, dim3 grid) {
+    hipLaunchKernelGGL((cfg_dpmpp_kernel<prev, v4>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2, (const float*)x,
+                       (const float*)x_base, (const float*)x0_prev, (float*)x_out, (float*)x0_out, (long)n, has_uncond, k);
+  });
   return af_check_launch("af_cfg_dpmpp_step");
 }
 
@@ -363,21 +373,11 @@ extern "C" int af_cfg_lcm_step(const void* eps2, const void* x, const void* nois
   AF_REQUIRE(!has_noise || (sqrt_a_next > 0.f && sqrt_a_next <= 1.f && sqrt_1ma_next >= 0.f && sqrt_1ma_next < 1.f),
              "af_cfg_lcm_step: need sqrt_a_next in (0, 1] and sqrt_1ma_next in [0, 1)");
   const LcmCoefs k{guidance, sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next, sqrt_1ma_next};
-  const uintptr_t align = reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_next) |
-                          reinterpret_cast<uintptr_t>(denoised) | (has_noise ? reinterpret_cast<uintptr_t>(noise) : 0);
-  const bool v4 = n % 4 == 0 && (align & 15) == 0;
-  const dim3 grid = grid1d(v4 ? n / 4 : n);
-  const auto *e = (const float*)eps2, *xx = (const float*)x, *nz = (const float*)noise;
-  auto *xn = (float*)x_next, *dn = (float*)denoised;
   AfLaunchScope scope(AF_FAM_ELEM, stream);
-  if (has_noise && v4)
-    hipLaunchKernelGGL((cfg_lcm_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, nz, xn, dn, (long)n, has_uncond, k);
-  else if (has_noise)
-    hipLaunchKernelGGL((cfg_lcm_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, nz, xn, dn, (long)n, has_uncond, k);
-  else if (v4)
-    hipLaunchKernelGGL((cfg_lcm_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, nz, xn, dn, (long)n, has_uncond, k);
-  else
-    hipLaunchKernelGGL((cfg_lcm_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, e, xx, nz, xn, dn, (long)n, has_uncond, k);
+  launch_flag_v4(has_noise, n, {eps2, x, x_next, denoised, noise}, [&](auto has_nz, auto v4, dim3 grid) {
+    hipLaunchKernelGGL((cfg_lcm_kernel<has_nz, v4>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2, (const float*)x,
+                       (const float*)noise, (float*)x_next, (float*)denoised, (long)n, has_uncond, k);
+  });
   return af_check_launch("af_cfg_lcm_step");
 }
 

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .... import ops
+from .sampling import Sampler
 
 ORIGINAL_INFERENCE_STEPS = 50
 TIMESTEP_SCALING = 10.0
@@ -54,97 +55,31 @@ def lcm_step_coefficients(alphas_cumprod, timesteps):
     return out
 
 
-class LCMSampler:
-    def __init__(self, model):
-        self.model = model
-        self.ddpm_num_timesteps = model.num_timesteps
+class LCMSampler(Sampler):
+    def timesteps(self, S):
+        return lcm_timesteps(S, self.ddpm_num_timesteps)
 
-    def _alphas_cumprod(self):
-        ac = self.model.alphas_cumprod.detach().double().cpu().numpy()
-        assert ac.shape[0] == self.ddpm_num_timesteps
-        return ac
+    def guidance_scales(self, n, guidance_scale):
+        return [guidance_scale] * n
 
-    @torch.no_grad()
-    def sample(self, S, batch_size, shape, conditioning=None, x_T=None, guidance_scale=1.0, unconditional_conditioning=None,
-               callback=None, img_callback=None, log_every_t=100, generator=None, **kwargs):
-        """S LCM steps from x_T (drawn with torch.randn when None).  Returns (latents, intermediates) like DDIMSampler.sample;
-        intermediates["x_inter"] / ["pred_x0"] (the denoised sample d) start with x_T and record the step with index n - 1 - i
-        (0 = last) when index % log_every_t == 0, and the first step.  ``generator`` draws the re-noising of every step but the last,
-        in step order, on its own device (the default CUDA generator when None)."""
-        C, H, W = shape
-        device = self.model.betas.device
-        img = torch.randn((batch_size, C, H, W), device=device) if x_T is None else x_T
-        return self._run(lcm_timesteps(S, self.ddpm_num_timesteps), img, conditioning, guidance_scale, unconditional_conditioning,
-                         callback, img_callback, log_every_t, generator)
+    @staticmethod
+    def runs_uncond(unconditional_conditioning, scale):
+        """diffusers' rule for LCM-LoRA: the (cond, uncond) batch runs only when an uncond is given and the guidance scale is above 1."""
+        return unconditional_conditioning is not None and scale > 1.0
 
-    def img2img_steps(self, S, strength):
-        """(n, t_first) of an img2img run over the S-step schedule: n = min(int(S * strength), S) steps, the last n of the schedule,
-        starting from the latent noised to lcm_timesteps(S)[S - n]."""
-        ts = lcm_timesteps(S, self.ddpm_num_timesteps)
-        if not 0 < strength <= 1:
-            raise ValueError(f"img2img strength must be in (0, 1], got {strength}")
-        n = min(int(S * strength), S)
-        if n == 0:
-            raise ValueError(f"img2img strength {strength} with {S} steps leaves no denoising step (int({S} * {strength}) = 0)")
-        return n, int(ts[S - n])
-
-    @torch.no_grad()
-    def sample_img2img(self, S, strength, batch_size, x_t, conditioning, guidance_scale=1.0, unconditional_conditioning=None,
-                       callback=None, img_callback=None, log_every_t=100, generator=None):
-        """Denoise x_t (noised to img2img_steps(S, strength)[1]) through the last n steps of the S-step schedule.
-        Returns (latents, intermediates) like sample()."""
-        n, _ = self.img2img_steps(S, strength)
-        if x_t.shape[0] != batch_size:
-            raise ValueError(f"x_t holds {x_t.shape[0]} latents, batch_size is {batch_size}")
-        ts = lcm_timesteps(S, self.ddpm_num_timesteps)[S - n:]
-        return self._run(ts, x_t, conditioning, guidance_scale, unconditional_conditioning, callback, img_callback, log_every_t,
-                         generator)
-
-    def _run(self, timesteps, img, cond, guidance_scale, uncond, callback, img_callback, log_every_t, generator):
+    def make_step(self, S, timesteps, generator):
+        """``generator`` draws the re-noising of every step but the last, in step order, on its own device (the default CUDA
+        generator when None)."""
         n = len(timesteps)
         coefs = lcm_step_coefficients(self._alphas_cumprod(), timesteps)
         device = self.model.betas.device
         gdev = generator.device if generator is not None else device
-        b = img.shape[0]
-        x = img.to(torch.float32).contiguous()
-        intermediates = {"x_inter": [x], "pred_x0": [x]}
-        has_uncond = unconditional_conditioning_used(uncond, guidance_scale)
-        for i, (t, (sa, sb, c_out, c_skip, sa_next, sb_next)) in enumerate(zip(timesteps, coefs)):
-            ts = torch.full((b,), int(t), device=device, dtype=torch.long)
-            e2 = self._eps2(x, cond, ts, uncond if has_uncond else None)
+
+        def step(i, x, t, c, uc, g):
+            sa, sb, c_out, c_skip, sa_next, sb_next = coefs[i]
+            e2, has_uncond = self._eps(x, t, c, uc, g)
             if i < n - 1:
                 noise = torch.randn(x.shape, generator=generator, device=gdev).to(device)
-                x, d = ops.cfg_lcm_step(e2, x, noise, guidance_scale, sa, sb, c_out, c_skip, sa_next, sb_next, has_uncond)
-            else:
-                x, d = ops.cfg_lcm_step(e2, x, None, guidance_scale, sa, sb, c_out, c_skip, has_uncond=has_uncond)
-            if callback:
-                callback(i)
-            if img_callback:
-                img_callback(d, i)
-            index = n - i - 1
-            if index % log_every_t == 0 or index == n - 1:
-                intermediates["x_inter"].append(x)
-                intermediates["pred_x0"].append(d)
-        return x, intermediates
-
-    def _eps2(self, x, c, t, unconditional_conditioning):
-        """The U-Net's [e_cond ; e_uncond] (or e_cond alone when unconditional_conditioning is None), batched as
-        DDIMSampler.p_sample_ddim batches it."""
-        if unconditional_conditioning is None:
-            e2 = self.model.apply_model(x, t, c)
-        else:
-            x_in = torch.cat([x] * 2)
-            t_in = torch.cat([t] * 2)
-            if isinstance(c, tuple):
-                c_c, prompt_in_c, extra_info = c
-                c_u, prompt_in_u, _ = unconditional_conditioning
-                c2 = (torch.cat([c_c, c_u]), sum([prompt_in_c, prompt_in_u], []), extra_info)  # (cond, uncond) order
-            else:
-                c2 = torch.cat([c, unconditional_conditioning])
-            e2 = self.model.apply_model(x_in, t_in, c2)
-        return e2.to(torch.float32).contiguous()
-
-
-def unconditional_conditioning_used(unconditional_conditioning, guidance_scale):
-    """diffusers' rule for LCM-LoRA: the (cond, uncond) batch runs only when an uncond is given and the guidance scale is above 1."""
-    return unconditional_conditioning is not None and guidance_scale > 1.0
+                return ops.cfg_lcm_step(e2, x, noise, g, sa, sb, c_out, c_skip, sa_next, sb_next, has_uncond)
+            return ops.cfg_lcm_step(e2, x, None, g, sa, sb, c_out, c_skip, has_uncond=has_uncond)
+        return step
