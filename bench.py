@@ -7,22 +7,31 @@ inference, 512x512 (latent 64x64), bs = 4 images/GPU with classifier-free guidan
 tokens) + guidance combine + DDIM update.  Synthetic latents / context, seeded random weights
 of the SD-1.5 architecture (no network for checkpoints).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
     python bench.py ... --dump-outputs DIR    (also writes what each leg's last timed step computed, DIR/<name>.npy: two builds
                                                run with the same arguments get the same inputs and can be compared output for output)
 
+A plain run does only what the headline figure needs: it builds the U-Net, warms up, times the K denoise steps and prints
+the JSON line with `roofline` and `cpu_baseline` null.  `--full` adds everything else the benchmark measures: the denoise
+leg's instrumented roofline pass and CPU-oracle baseline, and the training legs below (each with its per-iteration-type and
+instrumented passes, and the same legs again with every pass the reference runs).  --dump-outputs implies --full: the
+training legs' arrays depend on the global RNG draws of every pass before them, so only the whole sequence writes arrays
+that compare with another build's.
+
 N > 1: one process per GPU.  Started WITHOUT a launcher (`python bench.py --gpus 8`), this process touches no GPU and
 starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD (never an exec), relays its rank-0
 JSON line and exits with its code.  Inference has no exchange step: independent replicas, weak scaling,
-`value` = N*K steps / max-over-ranks time.  The same JSON line carries a `train` object: the Stage-1 distillation
+`value` = N*K steps / max-over-ranks time.  With --full the same JSON line carries a `train` object: the Stage-1 distillation
 micro-batch (BASELINE configs[2]/[3], reference main.py:618, 911-915) on the same ranks, data parallel with the bucketed
 RCCL gradient all-reduce overlapped with the backward -- `train.value` (images/s) at N = 1 and N = 8 is what north_star's
 ">= 6x training images/s" is read from -- and a `train_stage2` object: the compositional-distillation micro-batch (configs[4]).
-`--mode denoise` / `--mode train` / `--mode train2` run one leg only.  Defaults: 10 warm-up + 100 timed denoise steps (two whole
-50-step samplings), 12 + 12 micro-batches per training leg; ~45 s in all on one MI355X (wall time per leg is printed on stderr).
+`--mode denoise` / `--mode train` / `--mode train2` run one leg only, `--mode all` all three (the default under --full); a
+training leg picked with --mode runs as it does under --full.
+Defaults: 10 warm-up + 100 timed denoise steps (two whole 50-step samplings), 12 + 12 micro-batches per training leg; ~75 s
+in all on one MI355X with --full (wall time per leg is printed on stderr).
 
-The JSON line carries, besides the driver contract:
+The JSON line carries, besides the driver contract (with --full; null in a plain run):
   roofline     -- dominant kernel family (the MFMA GEMM / implicit-conv template): algorithmic
                   FLOPs (conv3x3 400.33 + Linear 233.28 + conv1x1 43.62 GFLOP per
                   U-Net sample at 77 tokens) / summed launch time measured with hipEvents on the
@@ -588,7 +597,7 @@ def run_denoise(args, ctx, dev):
         elapsed = float(tt.item())
 
     roofline = None
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         # instrumented pass: same steps, eager launches, hipEvents around every launch of each family.  The C = 320 cross-attention blocks
         # run here in their three-launch form (to_q GEMM, core, to_out GEMM) so that the families keep their definitions -- every projection
         # in the GEMM family, the 16 cores in `xattn`; the timed region above ran them as one launch each (af_xattn_fused, tiled form: profiles/r04g)
@@ -665,7 +674,7 @@ def run_denoise(args, ctx, dev):
         roofline["cross_attn_block"] = cross_attn_block_time(unet, ctx2, B, dev)
 
     cpu_baseline = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         from oracle import unet_oracle as O
         # 32 threads measured fastest for this op mix on the GPU box's 256-thread host (16: 3.1 s, 32: 2.8 s,
         # 64: 3.9 s, 256: 137 s per U-Net sample); the count actually used is what is reported.
@@ -748,8 +757,12 @@ def main():
     ap.add_argument("--prefetch-stream", type=int, default=int(os.environ.get("AF_PREFETCH_STREAM", "0")), metavar="DEPTH",
                     help="denoise leg: read the weights of launch i + DEPTH on a second stream of the captured graph while launch i runs (0 = off)")
     ap.add_argument("--prefetch-wgs", type=int, default=int(os.environ.get("AF_PREFETCH_WGS", "64")), help="workgroups per prefetch launch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed denoise steps, run everything else the benchmark measures: the denoise leg's instrumented roofline "
+                         "pass and CPU-oracle baseline and, as --mode all (the default with --full), the Stage-1 / Stage-2 training legs with "
+                         "their extra passes.  A training leg picked with --mode runs as it does under --full")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="skip the instrumented roofline passes (the denoise leg runs its pass only with --full)")
     ap.add_argument("--no-ffn-lora", action="store_true", help="train leg: without the U-Net's trainable FFN DoRA adapters")
     ap.add_argument("--train-steps", type=int, default=12, help="timed micro-batches of the train leg")
     ap.add_argument("--train-warmup", type=int, default=24, help="untimed micro-batches (the hipGraph segments of every signature are captured in here: the from-noise recon variant, p = 0.4, is captured at its SECOND draw -- 12 were not always enough, profiles/r05ai)")
@@ -761,15 +774,23 @@ def main():
     ap.add_argument("--no-train-graphs", action="store_true", help="train leg: launch every kernel from Python instead of replaying captured segments")
     ap.add_argument("--sync-debug", default=None, metavar="FILE", help="train legs: write the Python stack of every host<->device synchronisation "
                     "of the timed micro-batches to FILE (torch.cuda.set_sync_debug_mode); the timing of such a run is not a result")
-    ap.add_argument("--mode", choices=["all", "denoise", "train", "train2"], default="all",
-                    help="all (default): the headline denoise line (BASELINE configs[1]) carrying the Stage-1 training leg "
-                         "(configs[2]/[3]) as its `train` object; denoise / train: one leg only (train prints its own line)")
+    ap.add_argument("--mode", choices=["all", "denoise", "train", "train2"], default=None,
+                    help="all (default with --full): the headline denoise line (BASELINE configs[1]) carrying the Stage-1 / Stage-2 training legs "
+                         "(configs[2]/[3], [4]) as its `train` / `train_stage2` objects; denoise (default otherwise) / train / train2: one leg only "
+                         "(train and train2 print their own line)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after each leg's timed steps, write what its last step computed as DIR/<name>.npy (float32, <= 64 MB in all): "
-                         "denoise_x_prev, denoise_pred_x0, denoise_eps (denoise leg), train_loss, train_stage2_loss (training legs)")
+                         "denoise_x_prev, denoise_pred_x0, denoise_eps (denoise leg), train_loss, train_stage2_loss (training legs); implies --full")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        # the training legs' arrays depend on where the global RNG streams stand when they start, and every pass before them draws
+        # from those streams (the cross-attention timing's inputs, Stage 1's per-iteration-type and instrumented micro-batches before
+        # Stage 2): a run that dumps runs everything --full runs, so that its arrays compare output for output with any other build's
+        args.full = True
+    if args.mode is None:
+        args.mode = "all" if args.full else "denoise"
     ctx = dist_context()
     world, rank, local_rank, launched = ctx
     if args.gpus > 1 and not launched:

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 : > gpurun_out/$TAG.txt
 for rep in $(seq 1 $REPS); do
   for v in 0 1; do
-    env $VAR=$v python bench.py --mode denoise --steps 100 --warmup 10 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --mode denoise --steps 100 --warmup 10 --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('rep $rep $VAR=$v: ms_per_step', d['ms_per_step'], 'families', d['roofline'].get('families_ms_per_step'))" >> gpurun_out/$TAG.txt

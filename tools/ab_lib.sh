@@ -12,7 +12,7 @@ make -C /tmp/ab_build -j16 EXTRA="$FLAGS" > /tmp/ab_build/build.log 2>&1 || { ta
 for rep in $(seq 1 $REPS); do
   for arm in 0 1; do
     if [ $arm = 0 ]; then export AF_LIB=/tmp/ab_build/libadaface_hip.so; else unset AF_LIB; fi
-    python bench.py --mode denoise --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full --mode denoise --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('rep $rep arm $arm (0 = built with [$FLAGS], 1 = the tree): ms_per_step', d['ms_per_step'], 'families', d['roofline'].get('families_ms_per_step'))" >> gpurun_out/$TAG.txt

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Profiles of the default bench (run on the GPU box from the repo root):   bash tools/profile_round.sh r02j
-#   <tag>_bench_line.json        python bench.py (all legs)
+#   <tag>_bench_line.json        python bench.py --full (all legs)
 #   <tag>_bench_kernel_stats.txt rocprofv3 --kernel-trace --stats of the denoise leg, last 10 steps
 #   <tag>_train_kernel_stats.txt, <tag>_train2_kernel_stats.txt   rocprofv3 --kernel-trace --stats of the Stage-1 / Stage-2 training legs, last 6 micro-batches
 #   <tag>_hbm_traffic.json       two separate --pmc passes (FETCH_SIZE, WRITE_SIZE) of 6 eager denoise steps, per kernel family
@@ -9,7 +9,7 @@ set -u
 TAG=${1:-r02}
 OUT=$PWD/gpurun_out
 export TMPDIR=/tmp
-python3 bench.py > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
 rm -rf $OUT/${TAG}_trace $OUT/${TAG}_pmc_f $OUT/${TAG}_pmc_w
 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_trace -- python3 bench.py --mode denoise --steps 20 --warmup 3 --no-cpu-baseline --no-roofline > $OUT/${TAG}_trace.log 2>&1
 DB=$(find $OUT/${TAG}_trace -name "*_results.db" | head -1)
