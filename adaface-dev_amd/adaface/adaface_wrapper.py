@@ -22,6 +22,14 @@ picks how many of the last steps of the schedule run (``DDIMSampler.img2img_step
 (``LatentDiffusion.img2img_latents``: two fused kernels around the VAE encoder) and denoised by ``DDIMSampler.sample_img2img``
 (``DPMSolverSampler.sample_img2img`` under ``"dpm++"``).
 
+``pipeline_name="inpaint"`` is diffusers' ``StableDiffusionInpaintPipeline`` in its 4-channel U-Net branch (the SD-1.5 base model;
+INTEGRATION.md "Inpainting"): img2img's input images and ``ref_img_strength``, plus ``forward``'s ``mask_image`` (one PIL image or a
+list of 1 or ``out_image_count``; white = repaint; see ``inpaint_masks``).  It needs ``vae`` (an ``AutoencoderKL``) or
+``base_model_path`` at construction, else ``InpaintVAEMissing``.  The images are encoded once
+(``LatentDiffusion.inpaint_latents``) and ``sample_inpaint`` runs the img2img steps of the chosen sampler; after each step, in the
+same kernel, the latent outside the mask is replaced by the image latent noised to the next timestep (the image latent itself after
+the last step).
+
 ``default_scheduler_name="dpm++"`` (the reference's DPM-Solver++ scheduler, diffusers' ``DPMSolverSinglestepScheduler`` with its
 defaults; INTEGRATION.md "DPM-Solver++ scheduler") samples both pipelines with ``DPMSolverSampler`` instead of ``DDIMSampler``: the same
 (cond, uncond) batches and guidance rule, one fused guidance + DPM-Solver++ update per step, typically at 20-25 ``num_inference_steps``
@@ -34,8 +42,9 @@ constant, the (cond, uncond) batch runs only when the scale is above 1, and ``fo
 step but the last.  Nothing is downloaded: ``lcm_lora_path`` is a local file or an in-memory state dict.  ``fuse_lcm_lora`` /
 ``unfuse_lcm_lora`` change the weights only; the sampler follows ``use_lcm``.
 
-SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, inpainting, U-Net ensembles and
-the ConsistentID encoder are out of scope (external packages)."""
+SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, U-Net ensembles and the
+ConsistentID encoder are out of scope (external packages).  Of inpainting, 9-channel inpainting U-Nets, ``padding_mask_crop`` /
+pixel paste-back, caller-supplied ``masked_image_latents``, graph capture of the loop and automatic face masks are not built."""
 import re
 import zlib
 
@@ -81,8 +90,34 @@ def img2img_images_u8(images, out_image_count):
     return torch.from_numpy(np.stack(arrs))
 
 
+def inpaint_masks(mask_images, out_image_count, size):
+    """Inpainting mask preparation on the host: one PIL image or a list of 1 or ``out_image_count`` images, each converted to "L" and
+    resized (LANCZOS) to ``size`` = (W, H) of the prepared input images when it differs.  White means repaint: m = v >= 128
+    (v / 255 >= 0.5) at full resolution, then nearest-neighbour to the latent grid, m_lat[i, j] = m[8 i, 8 j].
+    Returns fp32 {0, 1} [B_mask, 1, H/8, W/8] on the CPU."""
+    from PIL import Image
+    masks = list(mask_images) if isinstance(mask_images, (list, tuple)) else [mask_images]
+    if len(masks) not in (1, out_image_count):
+        raise ValueError(f"inpainting takes 1 or out_image_count = {out_image_count} mask images, got {len(masks)}")
+    out = []
+    for im in masks:
+        if not isinstance(im, Image.Image):
+            raise ValueError(f"inpainting mask images must be PIL images, got {type(im).__name__}")
+        im = im.convert("L")
+        if im.size != tuple(size):
+            im = im.resize(tuple(size), resample=Image.LANCZOS)
+        out.append(np.asarray(im, dtype=np.uint8)[::8, ::8] >= 128)
+    return torch.from_numpy(np.stack(out)[:, None].astype(np.float32))
+
+
 # default_scheduler_name -> sampler class (a sampling.Sampler, as LCMSampler: sample / img2img_steps / sample_img2img)
 SCHEDULERS = {"ddim": DDIMSampler, "dpm++": DPMSolverSampler}
+
+
+class InpaintVAEMissing(ValueError, NotImplementedError):
+    """``pipeline_name="inpaint"`` with neither ``vae`` nor ``base_model_path``: nothing to encode the input images with.  A
+    ValueError; also a NotImplementedError, which is what ``pipeline_name="inpaint"`` raised before inpainting was built, so callers
+    that caught that keep working."""
 
 
 class LCMLoRAMissing(ValueError, NotImplementedError):
@@ -148,9 +183,12 @@ class AdaFaceWrapper(nn.Module):
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
                  lcm_lora_path=None, lcm_lora_scale=1.0):
         super().__init__()
-        if pipeline_name not in ("text2img", "img2img", None):
-            raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img and img2img paths (and None = face encoder only) "
-                                      "are built")
+        if pipeline_name not in ("text2img", "img2img", "inpaint", None):
+            raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img, img2img and inpaint paths (and None = face "
+                                      "encoder only) are built")
+        if pipeline_name == "inpaint" and vae is None and base_model_path is None:
+            raise InpaintVAEMissing("pipeline_name='inpaint' encodes its input images: pass vae (an AutoencoderKL, encoder + decoder) or "
+                                    "base_model_path (whose VAE is loaded)")
         if list(adaface_encoder_types) != ["arc2face"]:
             raise NotImplementedError("only the Arc2Face ID encoder is in scope (ConsistentID needs an external package)")
         if default_scheduler_name not in SCHEDULERS:
@@ -376,14 +414,21 @@ class AdaFaceWrapper(nn.Module):
     def forward(self, noise, prompt, prompt_embeds=None, negative_prompt=None, placeholder_tokens_pos="append", guidance_scale=6.0,
                 out_image_count=4, ref_img_strength=0.8, generator=None, ablate_prompt_only_placeholders=False,
                 ablate_prompt_no_placeholders=False, ablate_prompt_embed_type="ada", nonmix_prompt_emb_weight=0,
-                repeat_prompt_for_each_encoder=True, verbose=False):
+                repeat_prompt_for_each_encoder=True, verbose=False, mask_image=None):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
-        if self.pipeline_name == "img2img":
+        inpaint = self.pipeline_name == "inpaint"
+        if inpaint and mask_image is None:
+            raise ValueError("the inpaint pipeline needs mask_image (white = repaint)")
+        if not inpaint and mask_image is not None:
+            raise ValueError(f"mask_image is given but the pipeline is {self.pipeline_name!r}: only pipeline_name='inpaint' takes a mask")
+        if self.pipeline_name in ("img2img", "inpaint"):
             if self.vae is None or not hasattr(self.vae, "encode_q_sample"):
-                raise ValueError("the img2img pipeline encodes its input images: it needs an AutoencoderKL (encoder + decoder) as vae, "
-                                 f"got {type(self.vae).__name__ if self.vae is not None else None}")
+                raise ValueError(f"the {self.pipeline_name} pipeline encodes its input images: it needs an AutoencoderKL (encoder + "
+                                 f"decoder) as vae, got {type(self.vae).__name__ if self.vae is not None else None}")
             images_u8 = img2img_images_u8(noise, out_image_count)
+            if inpaint:
+                masks = inpaint_masks(mask_image, out_image_count, (images_u8.shape[2], images_u8.shape[1]))
             self._sampler().img2img_steps(self.num_inference_steps, ref_img_strength)    # refuse a bad strength before any work
         if prompt_embeds is None:
             pe, ne, _, _ = self.encode_prompt(prompt, negative_prompt, placeholder_tokens_pos=placeholder_tokens_pos,
@@ -408,6 +453,14 @@ class AdaFaceWrapper(nn.Module):
                                            first_stage_model=self.vae)
             latents, _ = sampler.sample_img2img(self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond,
                                                 guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
+            return self._to_pil(latents)
+        if inpaint:
+            _, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
+            x_start, z, n_fwd = self.ldm.inpaint_latents(images_u8.to(self.device), out_image_count, t_first, generator=generator,
+                                                         first_stage_model=self.vae, from_noise=ref_img_strength == 1)
+            latents, _ = sampler.sample_inpaint(self.num_inference_steps, ref_img_strength, out_image_count, x_start, z, n_fwd,
+                                                masks.to(self.device), cond, guidance_scale=guidance_scale,
+                                                unconditional_conditioning=uncond, generator=generator)
             return self._to_pil(latents)
         noise = noise.to(device=self.device, dtype=torch.float32)
         latents, _ = sampler.sample(self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise,

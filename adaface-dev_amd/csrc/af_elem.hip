@@ -106,24 +106,103 @@ __global__ void nhwc_to_nchw_kernel(const half_t* __restrict__ x, float* __restr
   y[idx] = (float)x[((long)b * HW + p) * cstride + c];
 }
 
+// inpainting: the mask blend as the tail of a fused step kernel (INTEGRATION.md "Inpainting" rule 4).  Per element of output b,
+// channel c, pixel p: x_next = m ? x_new : known, m = mask[b % B_mask][p] (binary: nonzero keeps x_new), known = sa z + sb noise
+// (BLEND_NOISED) or z (BLEND_CLEAN, the last step; noise is not read), z = z[b % B_img][c][p].  z fp32 [B_img,4,hw], noise fp32
+// [B,4,hw], mask fp32 [B_mask,1,hw].  BLEND_NONE is the plain step.  The V4 forms need hw % 4 == 0 (four elements share b and c).
+enum : int { BLEND_NONE = 0, BLEND_NOISED = 1, BLEND_CLEAN = 2 };
+
+struct InpaintBlend {
+  const float* z;
+  const float* noise;
+  const float* mask;
+  float sa, sb;
+  int B_img, B_mask;
+  long hw;
+};
+
+// offsets into z and mask of element i (the first of a float4 in the V4 forms); 32-bit, the entry points require n < 2^31
+__device__ __forceinline__ void blend_offsets(long i, const InpaintBlend& bl, long& zo, long& mo) {
+  const unsigned hw = (unsigned)bl.hw, chw = 4 * hw;
+  const unsigned b = (unsigned)i / chw, r = (unsigned)i - b * chw;
+  zo = (long)((b % (unsigned)bl.B_img) * chw + r);
+  mo = (long)((b % (unsigned)bl.B_mask) * hw + r % hw);
+}
+
+// known = fma(sb, noise, sa z), the rounding of af_vae_latents_q_sample's x_t
+template <int BLEND>
+__device__ __forceinline__ float blend_elem(float y, float m, float z, float nz, const InpaintBlend& bl) {
+  const float known = BLEND == BLEND_NOISED ? fmaf(bl.sb, nz, bl.sa * z) : z;
+  return m != 0.f ? y : known;
+}
+
+template <int BLEND>
+__device__ __forceinline__ float blend_scalar(float y, long i, const InpaintBlend& bl) {
+  if (BLEND == BLEND_NONE) return y;
+  long zo, mo;
+  blend_offsets(i, bl, zo, mo);
+  return blend_elem<BLEND>(y, bl.mask[mo], bl.z[zo], BLEND == BLEND_NOISED ? bl.noise[i] : 0.f, bl);
+}
+
+// y holds elements 4 i .. 4 i + 3
+template <int BLEND>
+__device__ __forceinline__ float4 blend_v4(float4 y, long i, const InpaintBlend& bl) {
+  if (BLEND == BLEND_NONE) return y;
+  long zo, mo;
+  blend_offsets(4 * i, bl, zo, mo);
+  const float4 m = *reinterpret_cast<const float4*>(bl.mask + mo);
+  const float4 z = *reinterpret_cast<const float4*>(bl.z + zo);
+  const float4 nz = BLEND == BLEND_NOISED ? reinterpret_cast<const float4*>(bl.noise)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  return make_float4(blend_elem<BLEND>(y.x, m.x, z.x, nz.x, bl), blend_elem<BLEND>(y.y, m.y, z.y, nz.y, bl),
+                     blend_elem<BLEND>(y.z, m.z, z.z, nz.z, bl), blend_elem<BLEND>(y.w, m.w, z.w, nz.w, bl));
+}
+
+// classifier-free guidance + one DDIM step (ddim.py:253-255, 279-301, sigma = 0), per element:
+// e = e_u + g (e_c - e_u); pred_x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t); x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev) e.
+// pred_x0 may be NULL.  V4: 16-byte accesses, n % 4 == 0, all pointers aligned (the plain step runs the scalar form only).
+struct DdimCoefs {
+  float g, sqrt_one_minus_at, sqrt_at, sqrt_aprev, dir_coef;
+};
+
+// The roundings are spelled out (two fmas, two products and their sum) so that every form computes what the plain step always has.
+__device__ __forceinline__ float ddim_elem(float ec, float eu, int has_uncond, float x, const DdimCoefs& k, float& p0) {
+#pragma clang fp contract(off)
+  const float e = has_uncond ? fmaf(k.g, ec - eu, eu) : ec;
+  p0 = fmaf(-k.sqrt_one_minus_at, e, x) / k.sqrt_at;
+  return k.sqrt_aprev * p0 + k.dir_coef * e;
+}
+
+template <int BLEND, bool V4>
 __global__ void cfg_ddim_kernel(const float* __restrict__ eps2, const float* __restrict__ x, float* __restrict__ x_prev,
-                                float* __restrict__ pred_x0, long n, int has_uncond, float g, float sqrt_one_minus_at,
-                                float sqrt_at, float sqrt_aprev, float dir_coef) {
+                                float* __restrict__ pred_x0, long n, int has_uncond, DdimCoefs k, InpaintBlend bl) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float e = eps2[i];
-  if (has_uncond) {
-    const float eu = eps2[n + i];
-    e = eu + g * (e - eu);
+  if (V4) {
+    if (i >= n / 4) return;
+    const float4 ec = reinterpret_cast<const float4*>(eps2)[i];
+    const float4 eu = has_uncond ? reinterpret_cast<const float4*>(eps2 + n)[i] : ec;
+    const float4 xv = reinterpret_cast<const float4*>(x)[i];
+    float4 y, p0;
+    y.x = ddim_elem(ec.x, eu.x, has_uncond, xv.x, k, p0.x);
+    y.y = ddim_elem(ec.y, eu.y, has_uncond, xv.y, k, p0.y);
+    y.z = ddim_elem(ec.z, eu.z, has_uncond, xv.z, k, p0.z);
+    y.w = ddim_elem(ec.w, eu.w, has_uncond, xv.w, k, p0.w);
+    if (pred_x0) reinterpret_cast<float4*>(pred_x0)[i] = p0;
+    reinterpret_cast<float4*>(x_prev)[i] = blend_v4<BLEND>(y, i, bl);
+  } else {
+    if (i >= n) return;
+    const float ec = eps2[i];
+    const float eu = has_uncond ? eps2[n + i] : ec;
+    float p0;
+    const float y = ddim_elem(ec, eu, has_uncond, x[i], k, p0);
+    if (pred_x0) pred_x0[i] = p0;
+    x_prev[i] = blend_scalar<BLEND>(y, i, bl);
   }
-  const float p0 = (x[i] - sqrt_one_minus_at * e) / sqrt_at;
-  if (pred_x0) pred_x0[i] = p0;
-  x_prev[i] = sqrt_aprev * p0 + dir_coef * e;
 }
 
 // classifier-free guidance + one DPM-Solver++ (2S, midpoint) step in data-prediction form, per element:
 // e = e_u + g (e_c - e_u); x0 = (x - sigma_s e) / alpha_s; x_out = c_base x_base + c0 x0 + c1 x0_prev.
 // HAS_PREV = false never touches x0_prev (the order-1 steps, c1 == 0).  V4: 16-byte accesses, n % 4 == 0, all pointers aligned.
+// The *_elem helpers spell out their roundings (fmaf, contraction off), so the scalar, 16-byte and blend forms agree bit for bit.
 struct DpmppCoefs {
   float g, sigma_s, alpha_s, c_base, c0, c1;
 };
@@ -131,18 +210,18 @@ struct DpmppCoefs {
 template <bool HAS_PREV>
 __device__ __forceinline__ float dpmpp_elem(float ec, float eu, int has_uncond, float x, float xb, float xp, const DpmppCoefs& k,
                                             float& x0) {
-  const float e = has_uncond ? eu + k.g * (ec - eu) : ec;
-  x0 = (x - k.sigma_s * e) / k.alpha_s;
-  float y = k.c_base * xb + k.c0 * x0;
-  if (HAS_PREV) y += k.c1 * xp;
-  return y;
+#pragma clang fp contract(off)
+  const float e = has_uncond ? fmaf(k.g, ec - eu, eu) : ec;
+  x0 = fmaf(-k.sigma_s, e, x) / k.alpha_s;
+  const float y = fmaf(k.c0, x0, k.c_base * xb);
+  return HAS_PREV ? fmaf(k.c1, xp, y) : y;
 }
 
-template <bool HAS_PREV, bool V4>
+template <bool HAS_PREV, bool V4, int BLEND = BLEND_NONE>
 __global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const float* __restrict__ eps2, const float* __restrict__ x,
                                                         const float* __restrict__ x_base, const float* __restrict__ x0_prev,
                                                         float* __restrict__ x_out, float* __restrict__ x0_out, long n, int has_uncond,
-                                                        DpmppCoefs k) {
+                                                        DpmppCoefs k, InpaintBlend bl) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (V4) {
     if (i >= n / 4) return;
@@ -157,7 +236,7 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const float* __restrict_
     y.z = dpmpp_elem<HAS_PREV>(ec.z, eu.z, has_uncond, xv.z, xb.z, xp.z, k, p0.z);
     y.w = dpmpp_elem<HAS_PREV>(ec.w, eu.w, has_uncond, xv.w, xb.w, xp.w, k, p0.w);
     reinterpret_cast<float4*>(x0_out)[i] = p0;
-    reinterpret_cast<float4*>(x_out)[i] = y;
+    reinterpret_cast<float4*>(x_out)[i] = blend_v4<BLEND>(y, i, bl);
   } else {
     if (i >= n) return;
     const float ec = eps2[i];
@@ -165,7 +244,7 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const float* __restrict_
     float p0;
     const float y = dpmpp_elem<HAS_PREV>(ec, eu, has_uncond, x[i], x_base[i], HAS_PREV ? x0_prev[i] : 0.f, k, p0);
     x0_out[i] = p0;
-    x_out[i] = y;
+    x_out[i] = blend_scalar<BLEND>(y, i, bl);
   }
 }
 
@@ -179,16 +258,18 @@ struct LcmCoefs {
 
 template <bool HAS_NOISE>
 __device__ __forceinline__ float lcm_elem(float ec, float eu, int has_uncond, float x, float nz, const LcmCoefs& k, float& d) {
-  const float e = has_uncond ? eu + k.g * (ec - eu) : ec;
-  const float x0 = (x - k.sb * e) / k.sa;
-  d = k.c_out * x0 + k.c_skip * x;
-  return HAS_NOISE ? k.sa_next * d + k.sb_next * nz : d;
+#pragma clang fp contract(off)
+  const float e = has_uncond ? fmaf(k.g, ec - eu, eu) : ec;
+  const float x0 = fmaf(-k.sb, e, x) / k.sa;
+  d = fmaf(k.c_skip, x, k.c_out * x0);
+  return HAS_NOISE ? fmaf(k.sb_next, nz, k.sa_next * d) : d;
 }
 
-template <bool HAS_NOISE, bool V4>
+template <bool HAS_NOISE, bool V4, int BLEND = BLEND_NONE>
 __global__ __launch_bounds__(256) void cfg_lcm_kernel(const float* __restrict__ eps2, const float* __restrict__ x,
                                                       const float* __restrict__ noise, float* __restrict__ x_next,
-                                                      float* __restrict__ denoised, long n, int has_uncond, LcmCoefs k) {
+                                                      float* __restrict__ denoised, long n, int has_uncond, LcmCoefs k,
+                                                      InpaintBlend bl) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (V4) {
     if (i >= n / 4) return;
@@ -202,7 +283,7 @@ __global__ __launch_bounds__(256) void cfg_lcm_kernel(const float* __restrict__ 
     y.z = lcm_elem<HAS_NOISE>(ec.z, eu.z, has_uncond, xv.z, nz.z, k, d.z);
     y.w = lcm_elem<HAS_NOISE>(ec.w, eu.w, has_uncond, xv.w, nz.w, k, d.w);
     reinterpret_cast<float4*>(denoised)[i] = d;
-    reinterpret_cast<float4*>(x_next)[i] = y;
+    reinterpret_cast<float4*>(x_next)[i] = blend_v4<BLEND>(y, i, bl);
   } else {
     if (i >= n) return;
     const float ec = eps2[i];
@@ -210,7 +291,7 @@ __global__ __launch_bounds__(256) void cfg_lcm_kernel(const float* __restrict__ 
     float d;
     const float y = lcm_elem<HAS_NOISE>(ec, eu, has_uncond, x[i], HAS_NOISE ? noise[i] : 0.f, k, d);
     denoised[i] = d;
-    x_next[i] = y;
+    x_next[i] = blend_scalar<BLEND>(y, i, bl);
   }
 }
 
@@ -238,11 +319,14 @@ __global__ __launch_bounds__(256) void image_u8_kernel(const unsigned char* __re
 
 // img2img latents: per latent pixel of image b, moments = quant_conv(h) (8 x 8 fp32 + bias), z = scale (mean + exp(0.5 clamp(logvar,
 // -30, 20)) n_post), and for every output j = b + r B_img:  x_t[j] = sa z + sb n_fwd[j].  h NHWC fp16 [B_img,hh,ww,8]; n_post fp32
-// NCHW [B_img,4,hh,ww]; n_fwd, x_t fp32 NCHW [B_out,4,hh,ww].  The 72 weights are wave-uniform loads.
+// NCHW [B_img,4,hh,ww]; n_fwd, x_t fp32 NCHW [B_out,4,hh,ww].  The 72 weights are wave-uniform loads.  WRITE_Z (inpainting) also
+// stores z, fp32 NCHW [B_img,4,hh,ww].
+template <bool WRITE_Z = false>
 __global__ __launch_bounds__(256) void vae_latents_q_sample_kernel(const half_t* __restrict__ h, const float* __restrict__ qw,
                                                                    const float* __restrict__ qb, const float* __restrict__ n_post,
                                                                    const float* __restrict__ n_fwd, float scale, float sa, float sb,
-                                                                   float* __restrict__ x_t, int B_img, int reps, long hw) {
+                                                                   float* __restrict__ x_t, int B_img, int reps, long hw,
+                                                                   float* __restrict__ z_out) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)B_img * hw) return;
   const int b = (int)(i / hw);
@@ -262,6 +346,7 @@ __global__ __launch_bounds__(256) void vae_latents_q_sample_kernel(const half_t*
     }
     logvar = fminf(fmaxf(logvar, -30.0f), 20.0f);
     z[c] = scale * (mean + expf(0.5f * logvar) * n_post[((long)b * 4 + c) * hw + p]);
+    if (WRITE_Z) z_out[((long)b * 4 + c) * hw + p] = z[c];
   }
   for (int r = 0; r < reps; ++r) {
     const long j = (long)b + (long)r * B_img;
@@ -280,14 +365,14 @@ __global__ void silu_kernel(const half_t* __restrict__ x, half_t* __restrict__ y
 
 inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
-// The launch of a fused sampler step KERNEL<FLAG, V4> over n fp32 elements: V4 (one thread per float4) when n % 4 == 0 and every
-// pointer in `ptrs` is 16-byte aligned (NULL for one the FLAG = false form never touches), else one thread per element.
-// `launch(flag, v4, grid)` gets FLAG and V4 as std::bool_constant, to instantiate the kernel with.
+// The launch of a fused sampler step KERNEL<FLAG, V4> over n fp32 elements: V4 (one thread per float4) when n % 4 == 0, `vec_ok`
+// holds and every pointer in `ptrs` is 16-byte aligned (NULL for one the FLAG = false form never touches), else one thread per
+// element.  `launch(flag, v4, grid)` gets FLAG and V4 as std::bool_constant, to instantiate the kernel with.
 template <typename Launch>
-void launch_flag_v4(bool flag, long n, std::initializer_list<const void*> ptrs, Launch launch) {
+void launch_flag_v4(bool flag, long n, std::initializer_list<const void*> ptrs, Launch launch, bool vec_ok = true) {
   uintptr_t align = 0;
   for (const void* p : ptrs) align |= reinterpret_cast<uintptr_t>(p);
-  const bool v4 = n % 4 == 0 && (align & 15) == 0;
+  const bool v4 = vec_ok && n % 4 == 0 && (align & 15) == 0;
   const dim3 grid = grid1d(v4 ? n / 4 : n);
   if (flag && v4)
     launch(std::true_type{}, std::true_type{}, grid);
@@ -325,60 +410,171 @@ extern "C" int af_nhwc_f16_to_nchw_f32(const void* x, void* y, int B, int C, int
   return af_check_launch("af_nhwc_f16_to_nchw_f32");
 }
 
+namespace {
+
+// argument checks and the descriptor of an inpaint step's blend; AF_OK or the af_fail code
+int make_blend(const char* who, int64_t n, const void* z, const void* noise, const void* mask, int B_img, int B_mask, int64_t hw,
+               float sa_next, float sb_next, InpaintBlend& bl) {
+  const std::string w(who);
+  AF_REQUIRE(z && mask && B_img > 0 && B_mask > 0 && hw > 0 && n % (4 * hw) == 0, w + ": bad blend argument");
+  AF_REQUIRE(n < (int64_t(1) << 31) && (int64_t)B_img * 4 * hw < (int64_t(1) << 31), w + ": blend needs fewer than 2^31 elements");
+  AF_REQUIRE(!noise || (std::isfinite(sa_next) && std::isfinite(sb_next)), w + ": blend coefficients must be finite");
+  bl = InpaintBlend{(const float*)z, (const float*)noise, (const float*)mask, sa_next, sb_next, B_img, B_mask, (long)hw};
+  return AF_OK;
+}
+
+// the step's launch with the blend's form: BLEND_NOISED when it has noise, else BLEND_CLEAN; V4 also needs hw % 4 == 0 and the
+// blend's pointers aligned.  launch(flag, v4, blend, grid) gets all three as compile-time constants.
+template <typename Launch>
+void launch_blend(bool flag, long n, std::initializer_list<const void*> ptrs, const InpaintBlend& bl, Launch launch) {
+  uintptr_t align = reinterpret_cast<uintptr_t>(bl.z) | reinterpret_cast<uintptr_t>(bl.noise) | reinterpret_cast<uintptr_t>(bl.mask);
+  for (const void* p : ptrs) align |= reinterpret_cast<uintptr_t>(p);
+  const bool noised = bl.noise != nullptr;
+  launch_flag_v4(flag, n, {(const void*)align}, [&](auto f, auto v4, dim3 grid) {
+    if (noised)
+      launch(f, v4, std::integral_constant<int, BLEND_NOISED>{}, grid);
+    else
+      launch(f, v4, std::integral_constant<int, BLEND_CLEAN>{}, grid);
+  }, bl.hw % 4 == 0);
+}
+
+// fp32 scalar arithmetic exactly as ddim.py:279-301 (torch.full(..., fp32).sqrt())
+DdimCoefs ddim_coefs(float guidance, float a_t, float a_prev) {
+  return DdimCoefs{guidance, sqrtf(1.0f - a_t), sqrtf(a_t), sqrtf(a_prev), sqrtf(1.0f - a_prev)};
+}
+
+}  // namespace
+
 extern "C" int af_cfg_ddim_step(const void* eps2, const void* x, void* x_prev, void* pred_x0, int64_t n, int has_uncond,
                                 float guidance, float a_t, float a_prev, void* stream) {
   AF_REQUIRE(eps2 && x && x_prev && n > 0, "af_cfg_ddim_step: bad argument");
   AF_REQUIRE(a_t > 0.f && a_t <= 1.f && a_prev > 0.f && a_prev <= 1.f, "af_cfg_ddim_step: alphas must be in (0, 1]");
-  // fp32 scalar arithmetic exactly as ddim.py:279-301 (torch.full(..., fp32).sqrt())
-  const float sqrt_one_minus_at = sqrtf(1.0f - a_t);
-  const float sqrt_at = sqrtf(a_t);
-  const float sqrt_aprev = sqrtf(a_prev);
-  const float dir_coef = sqrtf(1.0f - a_prev);
+  const DdimCoefs k = ddim_coefs(guidance, a_t, a_prev);
   AfLaunchScope scope(AF_FAM_ELEM, stream);
-  hipLaunchKernelGGL(cfg_ddim_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, (const float*)eps2, (const float*)x,
-                     (float*)x_prev, (float*)pred_x0, (long)n, has_uncond, guidance, sqrt_one_minus_at, sqrt_at, sqrt_aprev,
-                     dir_coef);
+  hipLaunchKernelGGL((cfg_ddim_kernel<BLEND_NONE, false>), grid1d(n), dim3(256), 0, (hipStream_t)stream, (const float*)eps2,
+                     (const float*)x, (float*)x_prev, (float*)pred_x0, (long)n, has_uncond, k, InpaintBlend{});
   return af_check_launch("af_cfg_ddim_step");
 }
+
+extern "C" int af_cfg_ddim_inpaint_step(const void* eps2, const void* x, void* x_prev, void* pred_x0, int64_t n, int has_uncond,
+                                        float guidance, float a_t, float a_prev, const void* z, const void* noise, const void* mask,
+                                        int B_img, int B_mask, int64_t hw, float sa_next, float sb_next, void* stream) {
+  AF_REQUIRE(eps2 && x && x_prev && n > 0, "af_cfg_ddim_inpaint_step: bad argument");
+  AF_REQUIRE(a_t > 0.f && a_t <= 1.f && a_prev > 0.f && a_prev <= 1.f, "af_cfg_ddim_inpaint_step: alphas must be in (0, 1]");
+  InpaintBlend bl;
+  if (int rc = make_blend("af_cfg_ddim_inpaint_step", n, z, noise, mask, B_img, B_mask, hw, sa_next, sb_next, bl)) return rc;
+  const DdimCoefs k = ddim_coefs(guidance, a_t, a_prev);
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  launch_blend(false, n, {eps2, x, x_prev, pred_x0}, bl, [&](auto, auto v4, auto blend, dim3 grid) {
+    hipLaunchKernelGGL((cfg_ddim_kernel<blend, v4>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2, (const float*)x,
+                       (float*)x_prev, (float*)pred_x0, (long)n, has_uncond, k, bl);
+  });
+  return af_check_launch("af_cfg_ddim_inpaint_step");
+}
+
+namespace {
+
+int dpmpp_check(const char* who, const void* eps2, const void* x, const void* x_base, const void* x0_prev, const void* x_out,
+                const void* x0_out, int64_t n, float guidance, float alpha_s, float sigma_s, float c_base, float c0, float c1) {
+  const std::string w(who);
+  AF_REQUIRE(eps2 && x && x_base && x_out && x0_out && n > 0, w + ": bad argument");
+  AF_REQUIRE(alpha_s > 0.f && alpha_s <= 1.f && sigma_s >= 0.f && sigma_s < 1.f, w + ": need alpha_s in (0, 1] and sigma_s in [0, 1)");
+  AF_REQUIRE(std::isfinite(guidance) && std::isfinite(c_base) && std::isfinite(c0) && std::isfinite(c1),
+             w + ": coefficients must be finite");
+  AF_REQUIRE(x0_prev || c1 == 0.f, w + ": x0_prev is NULL but c1 != 0");
+  return AF_OK;
+}
+
+}  // namespace
 
 extern "C" int af_cfg_dpmpp_step(const void* eps2, const void* x, const void* x_base, const void* x0_prev, void* x_out, void* x0_out,
                                  int64_t n, int has_uncond, float guidance, float alpha_s, float sigma_s, float c_base, float c0,
                                  float c1, void* stream) {
-  AF_REQUIRE(eps2 && x && x_base && x_out && x0_out && n > 0, "af_cfg_dpmpp_step: bad argument");
-  AF_REQUIRE(alpha_s > 0.f && alpha_s <= 1.f && sigma_s >= 0.f && sigma_s < 1.f,
-             "af_cfg_dpmpp_step: need alpha_s in (0, 1] and sigma_s in [0, 1)");
-  AF_REQUIRE(std::isfinite(guidance) && std::isfinite(c_base) && std::isfinite(c0) && std::isfinite(c1),
-             "af_cfg_dpmpp_step: coefficients must be finite");
+  if (int rc = dpmpp_check("af_cfg_dpmpp_step", eps2, x, x_base, x0_prev, x_out, x0_out, n, guidance, alpha_s, sigma_s, c_base, c0, c1))
+    return rc;
   const bool has_prev = c1 != 0.f;
-  AF_REQUIRE(x0_prev || !has_prev, "af_cfg_dpmpp_step: x0_prev is NULL but c1 != 0");
   const DpmppCoefs k{guidance, sigma_s, alpha_s, c_base, c0, c1};
   AfLaunchScope scope(AF_FAM_ELEM, stream);
   launch_flag_v4(has_prev, n, {eps2, x, x_base, x_out, x0_out, has_prev ? x0_prev : nullptr}, [&](auto prev, auto v4, dim3 grid) {
     hipLaunchKernelGGL((cfg_dpmpp_kernel<prev, v4>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2, (const float*)x,
-                       (const float*)x_base, (const float*)x0_prev, (float*)x_out, (float*)x0_out, (long)n, has_uncond, k);
+                       (const float*)x_base, (const float*)x0_prev, (float*)x_out, (float*)x0_out, (long)n, has_uncond, k,
+                       InpaintBlend{});
   });
   return af_check_launch("af_cfg_dpmpp_step");
 }
 
+extern "C" int af_cfg_dpmpp_inpaint_step(const void* eps2, const void* x, const void* x_base, const void* x0_prev, void* x_out,
+                                         void* x0_out, int64_t n, int has_uncond, float guidance, float alpha_s, float sigma_s,
+                                         float c_base, float c0, float c1, const void* z, const void* noise, const void* mask,
+                                         int B_img, int B_mask, int64_t hw, float sa_next, float sb_next, void* stream) {
+  if (int rc = dpmpp_check("af_cfg_dpmpp_inpaint_step", eps2, x, x_base, x0_prev, x_out, x0_out, n, guidance, alpha_s, sigma_s, c_base,
+                           c0, c1))
+    return rc;
+  InpaintBlend bl;
+  if (int rc = make_blend("af_cfg_dpmpp_inpaint_step", n, z, noise, mask, B_img, B_mask, hw, sa_next, sb_next, bl)) return rc;
+  const bool has_prev = c1 != 0.f;
+  const DpmppCoefs k{guidance, sigma_s, alpha_s, c_base, c0, c1};
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  launch_blend(has_prev, n, {eps2, x, x_base, x_out, x0_out, has_prev ? x0_prev : nullptr}, bl,
+               [&](auto prev, auto v4, auto blend, dim3 grid) {
+    hipLaunchKernelGGL((cfg_dpmpp_kernel<prev, v4, blend>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2,
+                       (const float*)x, (const float*)x_base, (const float*)x0_prev, (float*)x_out, (float*)x0_out, (long)n,
+                       has_uncond, k, bl);
+  });
+  return af_check_launch("af_cfg_dpmpp_inpaint_step");
+}
+
+namespace {
+
+int lcm_check(const char* who, const void* eps2, const void* x, const void* noise, const void* x_next, const void* denoised, int64_t n,
+              float guidance, float sqrt_a, float sqrt_1ma, float c_out, float c_skip, float sqrt_a_next, float sqrt_1ma_next) {
+  const std::string w(who);
+  AF_REQUIRE(eps2 && x && x_next && denoised && n > 0, w + ": bad argument");
+  AF_REQUIRE(sqrt_a > 0.f && sqrt_a <= 1.f && sqrt_1ma >= 0.f && sqrt_1ma < 1.f, w + ": need sqrt_a in (0, 1] and sqrt_1ma in [0, 1)");
+  AF_REQUIRE(std::isfinite(guidance) && std::isfinite(c_out) && std::isfinite(c_skip) && std::isfinite(sqrt_a_next) &&
+                 std::isfinite(sqrt_1ma_next),
+             w + ": coefficients must be finite");
+  AF_REQUIRE(!noise || (sqrt_a_next > 0.f && sqrt_a_next <= 1.f && sqrt_1ma_next >= 0.f && sqrt_1ma_next < 1.f),
+             w + ": need sqrt_a_next in (0, 1] and sqrt_1ma_next in [0, 1)");
+  return AF_OK;
+}
+
+}  // namespace
+
 extern "C" int af_cfg_lcm_step(const void* eps2, const void* x, const void* noise, void* x_next, void* denoised, int64_t n,
                                int has_uncond, float guidance, float sqrt_a, float sqrt_1ma, float c_out, float c_skip,
                                float sqrt_a_next, float sqrt_1ma_next, void* stream) {
-  AF_REQUIRE(eps2 && x && x_next && denoised && n > 0, "af_cfg_lcm_step: bad argument");
-  AF_REQUIRE(sqrt_a > 0.f && sqrt_a <= 1.f && sqrt_1ma >= 0.f && sqrt_1ma < 1.f,
-             "af_cfg_lcm_step: need sqrt_a in (0, 1] and sqrt_1ma in [0, 1)");
-  AF_REQUIRE(std::isfinite(guidance) && std::isfinite(c_out) && std::isfinite(c_skip) && std::isfinite(sqrt_a_next) &&
-                 std::isfinite(sqrt_1ma_next),
-             "af_cfg_lcm_step: coefficients must be finite");
+  if (int rc = lcm_check("af_cfg_lcm_step", eps2, x, noise, x_next, denoised, n, guidance, sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next,
+                         sqrt_1ma_next))
+    return rc;
   const bool has_noise = noise != nullptr;
-  AF_REQUIRE(!has_noise || (sqrt_a_next > 0.f && sqrt_a_next <= 1.f && sqrt_1ma_next >= 0.f && sqrt_1ma_next < 1.f),
-             "af_cfg_lcm_step: need sqrt_a_next in (0, 1] and sqrt_1ma_next in [0, 1)");
   const LcmCoefs k{guidance, sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next, sqrt_1ma_next};
   AfLaunchScope scope(AF_FAM_ELEM, stream);
   launch_flag_v4(has_noise, n, {eps2, x, x_next, denoised, noise}, [&](auto has_nz, auto v4, dim3 grid) {
     hipLaunchKernelGGL((cfg_lcm_kernel<has_nz, v4>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2, (const float*)x,
-                       (const float*)noise, (float*)x_next, (float*)denoised, (long)n, has_uncond, k);
+                       (const float*)noise, (float*)x_next, (float*)denoised, (long)n, has_uncond, k, InpaintBlend{});
   });
   return af_check_launch("af_cfg_lcm_step");
+}
+
+extern "C" int af_cfg_lcm_inpaint_step(const void* eps2, const void* x, const void* noise, void* x_next, void* denoised, int64_t n,
+                                       int has_uncond, float guidance, float sqrt_a, float sqrt_1ma, float c_out, float c_skip,
+                                       float sqrt_a_next, float sqrt_1ma_next, const void* z, const void* blend_noise,
+                                       const void* mask, int B_img, int B_mask, int64_t hw, float sa_next, float sb_next,
+                                       void* stream) {
+  if (int rc = lcm_check("af_cfg_lcm_inpaint_step", eps2, x, noise, x_next, denoised, n, guidance, sqrt_a, sqrt_1ma, c_out, c_skip,
+                         sqrt_a_next, sqrt_1ma_next))
+    return rc;
+  InpaintBlend bl;
+  if (int rc = make_blend("af_cfg_lcm_inpaint_step", n, z, blend_noise, mask, B_img, B_mask, hw, sa_next, sb_next, bl)) return rc;
+  const bool has_noise = noise != nullptr;
+  const LcmCoefs k{guidance, sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next, sqrt_1ma_next};
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  launch_blend(has_noise, n, {eps2, x, x_next, denoised, noise}, bl, [&](auto has_nz, auto v4, auto blend, dim3 grid) {
+    hipLaunchKernelGGL((cfg_lcm_kernel<has_nz, v4, blend>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2,
+                       (const float*)x, (const float*)noise, (float*)x_next, (float*)denoised, (long)n, has_uncond, k, bl);
+  });
+  return af_check_launch("af_cfg_lcm_inpaint_step");
 }
 
 extern "C" int af_q_sample(const void* x0, const void* noise, const void* sa, const void* sb, void* xt, int B, int64_t per,
@@ -399,18 +595,38 @@ extern "C" int af_image_u8_to_nhwc_f16(const void* img, void* out, int B, int H,
   return af_check_launch("af_image_u8_to_nhwc_f16");
 }
 
-extern "C" int af_vae_latents_q_sample(const void* h, const void* qw, const void* qb, const void* n_post, const void* n_fwd, float scale,
-                                       float sa, float sb, void* x_t, int B_img, int B_out, int hh, int ww, void* stream) {
-  AF_REQUIRE(h && qw && qb && n_post && n_fwd && x_t && B_img > 0 && B_out > 0 && hh > 0 && ww > 0,
-             "af_vae_latents_q_sample: bad argument");
-  AF_REQUIRE(B_out % B_img == 0, "af_vae_latents_q_sample: B_out must be a multiple of B_img");
-  AF_REQUIRE((reinterpret_cast<uintptr_t>(h) & 15) == 0, "af_vae_latents_q_sample: h must be 16-byte aligned");
+namespace {
+
+int vae_latents(const char* who, const void* h, const void* qw, const void* qb, const void* n_post, const void* n_fwd, float scale, float sa,
+                float sb, void* x_t, void* z, int B_img, int B_out, int hh, int ww, void* stream) {
+  const std::string w(who);
+  AF_REQUIRE(h && qw && qb && n_post && n_fwd && x_t && B_img > 0 && B_out > 0 && hh > 0 && ww > 0, w + ": bad argument");
+  AF_REQUIRE(B_out % B_img == 0, w + ": B_out must be a multiple of B_img");
+  AF_REQUIRE((reinterpret_cast<uintptr_t>(h) & 15) == 0, w + ": h must be 16-byte aligned");
   const long hw = (long)hh * ww;
   AfLaunchScope scope(AF_FAM_ELEM, stream);
-  hipLaunchKernelGGL(vae_latents_q_sample_kernel, grid1d((long)B_img * hw), dim3(256), 0, (hipStream_t)stream, (const half_t*)h,
-                     (const float*)qw, (const float*)qb, (const float*)n_post, (const float*)n_fwd, scale, sa, sb, (float*)x_t, B_img,
-                     B_out / B_img, hw);
-  return af_check_launch("af_vae_latents_q_sample");
+  if (z)
+    hipLaunchKernelGGL(vae_latents_q_sample_kernel<true>, grid1d((long)B_img * hw), dim3(256), 0, (hipStream_t)stream, (const half_t*)h,
+                       (const float*)qw, (const float*)qb, (const float*)n_post, (const float*)n_fwd, scale, sa, sb, (float*)x_t, B_img,
+                       B_out / B_img, hw, (float*)z);
+  else
+    hipLaunchKernelGGL(vae_latents_q_sample_kernel<false>, grid1d((long)B_img * hw), dim3(256), 0, (hipStream_t)stream, (const half_t*)h,
+                       (const float*)qw, (const float*)qb, (const float*)n_post, (const float*)n_fwd, scale, sa, sb, (float*)x_t, B_img,
+                       B_out / B_img, hw, nullptr);
+  return af_check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int af_vae_latents_q_sample(const void* h, const void* qw, const void* qb, const void* n_post, const void* n_fwd, float scale,
+                                       float sa, float sb, void* x_t, int B_img, int B_out, int hh, int ww, void* stream) {
+  return vae_latents("af_vae_latents_q_sample", h, qw, qb, n_post, n_fwd, scale, sa, sb, x_t, nullptr, B_img, B_out, hh, ww, stream);
+}
+
+extern "C" int af_vae_latents_z_q_sample(const void* h, const void* qw, const void* qb, const void* n_post, const void* n_fwd, float scale,
+                                         float sa, float sb, void* x_t, void* z, int B_img, int B_out, int hh, int ww, void* stream) {
+  AF_REQUIRE(z, "af_vae_latents_z_q_sample: z is NULL");
+  return vae_latents("af_vae_latents_z_q_sample", h, qw, qb, n_post, n_fwd, scale, sa, sb, x_t, z, B_img, B_out, hh, ww, stream);
 }
 
 // dS = P * (dP - rowsum(P * dP)): the softmax backward of the VAE decoder's single-head attention (rows like af_softmax_rows)

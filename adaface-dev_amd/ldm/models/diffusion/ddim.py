@@ -64,22 +64,24 @@ class DDIMSampler(Sampler):
         return self._run(np.flip(timesteps), img, cond_context, unconditional_conditioning, guidance_scale, callback, img_callback,
                          log_every_t, self._step(len(timesteps), mask, x0))
 
-    def make_step(self, S, timesteps, generator):      # sample_img2img's steps; sample() runs ddim_sampling
+    def make_step(self, S, timesteps, generator, blends=None):      # img2img / inpaint steps; sample() runs ddim_sampling
         self.make_schedule(ddim_num_steps=S, ddim_eta=0.0, verbose=False)
-        return self._step(len(timesteps))
+        return self._step(len(timesteps), blends=blends)
 
-    def _step(self, n, mask=None, x0=None):
-        """Step i of a run over the first n timesteps of the schedule: p_sample_ddim at index n - 1 - i, after the mask blend."""
+    def _step(self, n, mask=None, x0=None, blends=None):
+        """Step i of a run over the first n timesteps of the schedule: p_sample_ddim at index n - 1 - i, after the LDM mask blend
+        (``mask`` / ``x0``) or with the inpaint blend ``blends[i]`` fused into it."""
         def step(i, x, t, c, uc, g):
             if mask is not None:
                 assert x0 is not None
                 x = (self.model.q_sample(x0, t) * mask + (1.0 - mask) * x).contiguous()
-            return self.p_sample_ddim(x, c, t, index=n - 1 - i, guidance_scale=g, unconditional_conditioning=uc)
+            return self.p_sample_ddim(x, c, t, index=n - 1 - i, guidance_scale=g, unconditional_conditioning=uc,
+                                      blend=None if blends is None else blends[i])
         return step
 
     @torch.no_grad()
-    def p_sample_ddim(self, x, c, t, index, guidance_scale=1.0, unconditional_conditioning=None, **kwargs):
-        """One DDIM step (ddim.py:223-302, eta = 0)."""
+    def p_sample_ddim(self, x, c, t, index, guidance_scale=1.0, unconditional_conditioning=None, blend=None, **kwargs):
+        """One DDIM step (ddim.py:223-302, eta = 0); ``blend``: an ops.InpaintBlend applied to x_prev in the same kernel."""
         e2, has_uncond = self._eps(x, t, c, unconditional_conditioning, guidance_scale)
         a_t, a_prev = float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index])
-        return ops.cfg_ddim_step(e2, x.to(torch.float32).contiguous(), guidance_scale, a_t, a_prev, has_uncond)
+        return ops.cfg_ddim_step(e2, x.to(torch.float32).contiguous(), guidance_scale, a_t, a_prev, has_uncond, blend=blend)

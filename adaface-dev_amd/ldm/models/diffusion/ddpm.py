@@ -388,6 +388,19 @@ class LatentDiffusion(CompReconLossesMixin, nn.Module):
         j % B_img and shares its posterior sample.  Noise: n_post [B_img, 4, h, w] first, then n_fwd [out_count, 4, h, w], both
         torch.randn on the generator's device (the default CUDA generator when None), moved to the model's device.
         ``first_stage_model``: an AutoencoderKL to use instead of ``self.first_stage_model``."""
+        return self._encode_latents(images_u8, out_count, t, generator, first_stage_model)[0]
+
+    @torch.no_grad()
+    def inpaint_latents(self, images_u8, out_count, t, generator=None, first_stage_model=None, from_noise=False):
+        """The inpainting latents (INTEGRATION.md "Inpainting" rule 3): (x_start, z, n_fwd), drawn and encoded as img2img_latents.
+        z fp32 [B_img, 4, H/8, W/8] are the image latents the steps blend with, n_fwd fp32 [out_count, 4, H/8, W/8] the start noise.
+        x_start is the img2img start latent noised to timestep t, or n_fwd itself when ``from_noise`` (strength 1, diffusers'
+        is_strength_max)."""
+        x_t, z, n_fwd = self._encode_latents(images_u8, out_count, t, generator, first_stage_model, with_z=True)
+        return (n_fwd if from_noise else x_t), z, n_fwd
+
+    def _encode_latents(self, images_u8, out_count, t, generator, first_stage_model, with_z=False):
+        """img2img_latents' draws and encode: (x_t,), or (x_t, z, n_fwd) ``with_z``."""
         vae = first_stage_model if first_stage_model is not None else self.first_stage_model
         if vae is None or not hasattr(vae, "encode_q_sample"):
             raise ValueError("img2img needs a first-stage model with an encoder (AutoencoderKL); "
@@ -402,7 +415,9 @@ class LatentDiffusion(CompReconLossesMixin, nn.Module):
         n_fwd = torch.randn((out_count,) + lat, generator=generator, device=gdev).to(dev)
         t = int(t)
         sa, sb = float(self.sqrt_alphas_cumprod[t]), float(self.sqrt_one_minus_alphas_cumprod[t])
-        return vae.encode_q_sample(images_u8.to(dev).contiguous(), n_post.contiguous(), n_fwd.contiguous(), self.scale_factor, sa, sb)
+        n_fwd = n_fwd.contiguous()
+        out = vae.encode_q_sample(images_u8.to(dev).contiguous(), n_post.contiguous(), n_fwd, self.scale_factor, sa, sb, with_z=with_z)
+        return (*out, n_fwd) if with_z else (out,)
 
     def q_sample(self, x_start, t, noise=None):
         noise = torch.randn_like(x_start) if noise is None else noise

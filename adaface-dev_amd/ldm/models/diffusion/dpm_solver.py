@@ -76,7 +76,7 @@ class DPMSolverSampler(Sampler):
     def timesteps(self, S):
         return dpmpp_timesteps(S, self.ddpm_num_timesteps)
 
-    def make_step(self, S, timesteps, generator):
+    def make_step(self, S, timesteps, generator, blends=None):
         coefs = dpmpp_step_coefficients(self._alphas_cumprod(), timesteps, dpmpp_orders(len(timesteps)))
         x_blk = x0_blk = None
 
@@ -85,7 +85,8 @@ class DPMSolverSampler(Sampler):
             a_s, s_s, c_base, c0, c1, uses_blk = coefs[i]
             e2, has_uncond = self._eps(x, t, c, uc, g)
             x_base, x0_prev = (x_blk, x0_blk) if uses_blk else (x, None)
-            x_new, x0 = ops.cfg_dpmpp_step(e2, x, x_base, x0_prev, g, a_s, s_s, c_base, c0, c1, has_uncond)
+            x_new, x0 = ops.cfg_dpmpp_step(e2, x, x_base, x0_prev, g, a_s, s_s, c_base, c0, c1, has_uncond,
+                                           blend=None if blends is None else blends[i])
             if not uses_blk:
                 x_blk, x0_blk = x, x0          # an order-1 step starts the block of the step after it
             return x_new, x0

@@ -67,7 +67,7 @@ class LCMSampler(Sampler):
         """diffusers' rule for LCM-LoRA: the (cond, uncond) batch runs only when an uncond is given and the guidance scale is above 1."""
         return unconditional_conditioning is not None and scale > 1.0
 
-    def make_step(self, S, timesteps, generator):
+    def make_step(self, S, timesteps, generator, blends=None):
         """``generator`` draws the re-noising of every step but the last, in step order, on its own device (the default CUDA
         generator when None)."""
         n = len(timesteps)
@@ -78,8 +78,9 @@ class LCMSampler(Sampler):
         def step(i, x, t, c, uc, g):
             sa, sb, c_out, c_skip, sa_next, sb_next = coefs[i]
             e2, has_uncond = self._eps(x, t, c, uc, g)
+            blend = None if blends is None else blends[i]
             if i < n - 1:
                 noise = torch.randn(x.shape, generator=generator, device=gdev).to(device)
-                return ops.cfg_lcm_step(e2, x, noise, g, sa, sb, c_out, c_skip, sa_next, sb_next, has_uncond)
-            return ops.cfg_lcm_step(e2, x, None, g, sa, sb, c_out, c_skip, has_uncond=has_uncond)
+                return ops.cfg_lcm_step(e2, x, noise, g, sa, sb, c_out, c_skip, sa_next, sb_next, has_uncond, blend=blend)
+            return ops.cfg_lcm_step(e2, x, None, g, sa, sb, c_out, c_skip, has_uncond=has_uncond, blend=blend)
         return step

@@ -5,7 +5,11 @@ A sampler subclasses ``Sampler`` and gives only what makes it different: its des
 guidance policy (``guidance_scales`` and ``runs_uncond``) and, per run, its step (``make_step``): the U-Net call and the fused
 gfx950 kernel of one step, with whatever state the steps of a run share.
 """
+import math
+
 import torch
+
+from .... import ops
 
 
 def guide_scales(n, guidance_scale):
@@ -35,9 +39,10 @@ class Sampler:
         """The timesteps of an S-step run, descending."""
         raise NotImplementedError
 
-    def make_step(self, S, timesteps, generator):
+    def make_step(self, S, timesteps, generator, blends=None):
         """step(i, x, t, cond, uncond, guidance_scale) -> (x_next, x0) for step i of a run over ``timesteps``, the last
-        len(timesteps) of the S-step schedule.  ``generator`` draws whatever the steps draw."""
+        len(timesteps) of the S-step schedule.  ``generator`` draws whatever the steps draw.  ``blends`` (inpainting): one
+        ops.InpaintBlend per step, which the step's fused kernel applies to x_next."""
         raise NotImplementedError
 
     def guidance_scales(self, n, guidance_scale):
@@ -82,6 +87,15 @@ class Sampler:
             raise ValueError(f"img2img strength {strength} with {S} steps leaves no denoising step (int({S} * {strength}) = 0)")
         return n, int(self.timesteps(S)[-n])
 
+    def inpaint_blends(self, timesteps, z, noise, mask):
+        """The blend of each step of an inpaint run over ``timesteps`` (INTEGRATION.md "Inpainting" rule 4): after step i the
+        known region is z noised with ``noise`` to timesteps[i + 1], (sa, sb) = (sqrt(abar), sqrt(1 - abar)) in fp64, and z
+        itself after the last step."""
+        ac = self._alphas_cumprod()
+        ts = [int(t) for t in timesteps]
+        nxt = [ops.InpaintBlend(z, noise, mask, math.sqrt(ac[t]), math.sqrt(1.0 - ac[t])) for t in ts[1:]]
+        return nxt + [ops.InpaintBlend(z, None, mask)]
+
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, x_T=None, guidance_scale=1.0, unconditional_conditioning=None,
                callback=None, img_callback=None, log_every_t=100, generator=None, **kwargs):
@@ -104,6 +118,23 @@ class Sampler:
         ts = self.timesteps(S)[-n:]
         return self._run(ts, x_t, conditioning, unconditional_conditioning, guidance_scale, callback, img_callback, log_every_t,
                          self.make_step(S, ts, generator))
+
+    @torch.no_grad()
+    def sample_inpaint(self, S, strength, batch_size, x_start, z, noise, mask, conditioning, guidance_scale=1.0,
+                       unconditional_conditioning=None, callback=None, img_callback=None, log_every_t=100, generator=None):
+        """sample_img2img's steps from x_start (e.g. LatentDiffusion.inpaint_latents), each followed in its kernel by the mask blend
+        of inpaint_blends: where ``mask`` (fp32 {0, 1} [B_mask, 1, h, w], 1 = repaint) is 0, the latent handed on is the image
+        latent z [B_img, 4, h, w] noised with ``noise`` (the start noise [batch_size, 4, h, w]) to the next timestep, and z itself
+        after the last step.  Output b uses z[b % B_img] and mask[b % B_mask].  Returns (latents, intermediates) like sample()."""
+        n, _ = self.img2img_steps(S, strength)
+        for name, t in (("x_start", x_start), ("noise", noise)):
+            if t.shape[0] != batch_size:
+                raise ValueError(f"{name} holds {t.shape[0]} latents, batch_size is {batch_size}")
+        ts = self.timesteps(S)[-n:]
+        blends = self.inpaint_blends(ts, z.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous(),
+                                     mask.to(torch.float32).contiguous())
+        return self._run(ts, x_start, conditioning, unconditional_conditioning, guidance_scale, callback, img_callback, log_every_t,
+                         self.make_step(S, ts, generator, blends))
 
     def _run(self, timesteps, img, cond, uncond, guidance_scale, callback, img_callback, log_every_t, step):
         """step() over ``timesteps`` (descending) from img.  Returns (latents, intermediates); intermediates["x_inter"] /

@@ -503,13 +503,14 @@ class AutoencoderKL(AutoencoderKLDecoder):
         return self._qc
 
     @torch.no_grad()
-    def encode_q_sample(self, images_u8, n_post, n_fwd, scale, sa, sb):
+    def encode_q_sample(self, images_u8, n_post, n_fwd, scale, sa, sb, with_z=False):
         """img2img start latents: uint8 RGB [B_img, H, W, 3] on the device -> x_t fp32 [B_out, 4, H/8, W/8] =
         sa * scale * (mean + exp(0.5 logvar) * n_post) + sb * n_fwd, output j from image j % B_img (n_post [B_img, 4, H/8, W/8],
-        n_fwd [B_out, 4, H/8, W/8] fp32).  Three launch groups: af_image_u8_to_nhwc_f16, the encoder, af_vae_latents_q_sample."""
+        n_fwd [B_out, 4, H/8, W/8] fp32).  Three launch groups: af_image_u8_to_nhwc_f16, the encoder, af_vae_latents_q_sample.
+        ``with_z`` returns (x_t, z) with the image latents z = scale * (mean + ...) fp32 [B_img, 4, H/8, W/8] (inpainting)."""
         _require_cuda(self.quant_conv.weight, "AutoencoderKL")
         if self.quant_conv.in_channels != 8 or self.quant_conv.out_channels != 8:
             raise NotImplementedError("encode_q_sample needs the z_channels = embed_dim = 4 first stage (8 moment channels)")
         h = self.encoder.hip(ops.image_u8_to_nhwc_f16(images_u8))
         qw, qb = self._qc_pack()
-        return ops.vae_latents_q_sample(h, qw, qb, n_post, n_fwd, scale, sa, sb, n_fwd.shape[0])
+        return ops.vae_latents_q_sample(h, qw, qb, n_post, n_fwd, scale, sa, sb, n_fwd.shape[0], with_z=with_z)

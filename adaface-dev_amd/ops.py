@@ -927,21 +927,56 @@ def silu(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
-def cfg_ddim_step(eps2: torch.Tensor, x: torch.Tensor, guidance: float, a_t: float, a_prev: float, has_uncond: bool = True):
-    """eps2 fp32 [2n or n] = [e_cond ; e_uncond], x fp32 [n] -> (x_prev, pred_x0), ddim.py:253-302 (sigma = 0)."""
+@dataclass
+class InpaintBlend:
+    """The mask blend an inpaint step applies to its new latent x_new [B, 4, h, w] (INTEGRATION.md "Inpainting" rule 4):
+    x_next = mask ? x_new : known, known = fma(sb, noise, sa z), or z itself when noise is None (the last step).  z fp32
+    [B_img, 4, h, w] and mask fp32 {0, 1} [B_mask, 1, h, w] broadcast by b % B_img / b % B_mask; noise fp32 [B, 4, h, w]."""
+    z: torch.Tensor
+    noise: Optional[torch.Tensor]
+    mask: torch.Tensor
+    sa: float = 0.0
+    sb: float = 0.0
+
+    def args(self, x: torch.Tensor):
+        """The blend's C-ABI arguments for a step on x [B, 4, h, w], after checking shapes, dtypes and devices."""
+        if x.dim() != 4 or x.shape[1] != 4:
+            raise RuntimeError(f"inpaint step: x must be [B, 4, h, w], got {tuple(x.shape)}")
+        B, _, h, w = x.shape
+        want = [("z", self.z, 4, None), ("mask", self.mask, 1, None)]
+        if self.noise is not None:
+            want.append(("noise", self.noise, 4, B))
+        for name, t, c, b in want:
+            if t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() or t.dim() != 4 or \
+                    tuple(t.shape[1:]) != (c, h, w) or (b is not None and t.shape[0] != b) or t.shape[0] < 1:
+                raise RuntimeError(f"inpaint blend.{name}: expected contiguous fp32 [{b or 'N'}, {c}, {h}, {w}] on {x.device}, got "
+                                   f"{t.dtype} {tuple(t.shape)} on {t.device}")
+        return [_p(self.z), None if self.noise is None else _p(self.noise), _p(self.mask), self.z.shape[0], self.mask.shape[0],
+                h * w, float(self.sa), float(self.sb)]
+
+
+def cfg_ddim_step(eps2: torch.Tensor, x: torch.Tensor, guidance: float, a_t: float, a_prev: float, has_uncond: bool = True,
+                  blend: Optional[InpaintBlend] = None):
+    """eps2 fp32 [2n or n] = [e_cond ; e_uncond], x fp32 [n] -> (x_prev, pred_x0), ddim.py:253-302 (sigma = 0).  With ``blend``
+    (x [B, 4, h, w]), x_prev is blended (af_cfg_ddim_inpaint_step); pred_x0 is not."""
     assert eps2.dtype == torch.float32 and x.dtype == torch.float32 and eps2.is_contiguous() and x.is_contiguous()
     n = x.numel()
     assert eps2.numel() == (2 * n if has_uncond else n)
     x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
-    _lib.check(_lib.lib().af_cfg_ddim_step(_p(eps2), _p(x), _p(x_prev), _p(pred_x0), n, int(has_uncond), float(guidance),
-                                           float(a_t), float(a_prev), _stream()), "af_cfg_ddim_step")
+    args = [_p(eps2), _p(x), _p(x_prev), _p(pred_x0), n, int(has_uncond), float(guidance), float(a_t), float(a_prev)]
+    if blend is None:
+        _lib.check(_lib.lib().af_cfg_ddim_step(*args, _stream()), "af_cfg_ddim_step")
+    else:
+        _lib.check(_lib.lib().af_cfg_ddim_inpaint_step(*args, *blend.args(x), _stream()), "af_cfg_ddim_inpaint_step")
     return x_prev, pred_x0
 
 
 def cfg_dpmpp_step(eps2: torch.Tensor, x: torch.Tensor, x_base: torch.Tensor, x0_prev: Optional[torch.Tensor], guidance: float,
-                   alpha_s: float, sigma_s: float, c_base: float, c0: float, c1: float, has_uncond: bool = True):
+                   alpha_s: float, sigma_s: float, c_base: float, c0: float, c1: float, has_uncond: bool = True,
+                   blend: Optional[InpaintBlend] = None):
     """eps2 fp32 [2n or n] = [e_cond ; e_uncond], x / x_base / x0_prev fp32 [n] -> (x_out, x0_out): one DPM-Solver++ step,
-    x0 = (x - sigma_s e) / alpha_s, x_out = c_base x_base + c0 x0 + c1 x0_prev (x0_prev unused, may be None, when c1 == 0)."""
+    x0 = (x - sigma_s e) / alpha_s, x_out = c_base x_base + c0 x0 + c1 x0_prev (x0_prev unused, may be None, when c1 == 0).
+    With ``blend`` (x [B, 4, h, w]), x_out is blended (af_cfg_dpmpp_inpaint_step); x0_out is not."""
     assert eps2.dtype == torch.float32 and x.dtype == torch.float32 and eps2.is_contiguous() and x.is_contiguous()
     n = x.numel()
     assert eps2.numel() == (2 * n if has_uncond else n)
@@ -950,26 +985,34 @@ def cfg_dpmpp_step(eps2: torch.Tensor, x: torch.Tensor, x_base: torch.Tensor, x0
         assert x0_prev is not None and x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == n
     x_out, x0_out = torch.empty_like(x), torch.empty_like(x)
     prev = _p(x0_prev) if c1 != 0.0 else None
-    _lib.check(_lib.lib().af_cfg_dpmpp_step(_p(eps2), _p(x), _p(x_base), prev, _p(x_out), _p(x0_out), n, int(has_uncond),
-                                            float(guidance), float(alpha_s), float(sigma_s), float(c_base), float(c0), float(c1),
-                                            _stream()), "af_cfg_dpmpp_step")
+    args = [_p(eps2), _p(x), _p(x_base), prev, _p(x_out), _p(x0_out), n, int(has_uncond), float(guidance), float(alpha_s),
+            float(sigma_s), float(c_base), float(c0), float(c1)]
+    if blend is None:
+        _lib.check(_lib.lib().af_cfg_dpmpp_step(*args, _stream()), "af_cfg_dpmpp_step")
+    else:
+        _lib.check(_lib.lib().af_cfg_dpmpp_inpaint_step(*args, *blend.args(x), _stream()), "af_cfg_dpmpp_inpaint_step")
     return x_out, x0_out
 
 
 def cfg_lcm_step(eps2: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tensor], guidance: float, sqrt_a: float, sqrt_1ma: float,
-                 c_out: float, c_skip: float, sqrt_a_next: float = 0.0, sqrt_1ma_next: float = 0.0, has_uncond: bool = True):
+                 c_out: float, c_skip: float, sqrt_a_next: float = 0.0, sqrt_1ma_next: float = 0.0, has_uncond: bool = True,
+                 blend: Optional[InpaintBlend] = None):
     """eps2 fp32 [2n or n] = [e_cond ; e_uncond], x / noise fp32 [n] -> (x_next, denoised): one LCM step,
     x0 = (x - sqrt_1ma e) / sqrt_a, denoised = c_out x0 + c_skip x, x_next = sqrt_a_next denoised + sqrt_1ma_next noise
-    (noise None: the last step, x_next = denoised)."""
+    (noise None: the last step, x_next = denoised).  With ``blend`` (x [B, 4, h, w]), x_next is blended
+    (af_cfg_lcm_inpaint_step); denoised is not."""
     assert eps2.dtype == torch.float32 and x.dtype == torch.float32 and eps2.is_contiguous() and x.is_contiguous()
     n = x.numel()
     assert eps2.numel() == (2 * n if has_uncond else n)
     if noise is not None:
         assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == n
     x_next, denoised = torch.empty_like(x), torch.empty_like(x)
-    _lib.check(_lib.lib().af_cfg_lcm_step(_p(eps2), _p(x), None if noise is None else _p(noise), _p(x_next), _p(denoised), n,
-                                          int(has_uncond), float(guidance), float(sqrt_a), float(sqrt_1ma), float(c_out), float(c_skip),
-                                          float(sqrt_a_next), float(sqrt_1ma_next), _stream()), "af_cfg_lcm_step")
+    args = [_p(eps2), _p(x), None if noise is None else _p(noise), _p(x_next), _p(denoised), n, int(has_uncond), float(guidance),
+            float(sqrt_a), float(sqrt_1ma), float(c_out), float(c_skip), float(sqrt_a_next), float(sqrt_1ma_next)]
+    if blend is None:
+        _lib.check(_lib.lib().af_cfg_lcm_step(*args, _stream()), "af_cfg_lcm_step")
+    else:
+        _lib.check(_lib.lib().af_cfg_lcm_inpaint_step(*args, *blend.args(x), _stream()), "af_cfg_lcm_inpaint_step")
     return x_next, denoised
 
 
@@ -996,10 +1039,11 @@ def image_u8_to_nhwc_f16(img_u8: torch.Tensor) -> torch.Tensor:
 
 
 def vae_latents_q_sample(h: torch.Tensor, qw: torch.Tensor, qb: torch.Tensor, n_post: torch.Tensor, n_fwd: torch.Tensor, scale: float,
-                         sa: float, sb: float, out_count: int) -> torch.Tensor:
+                         sa: float, sb: float, out_count: int, with_z: bool = False):
     """Encoder output h fp16 [B_img, hh, ww, 8] -> x_t fp32 [out_count, 4, hh, ww]: quant_conv (qw fp32 [8, 8] out x in, qb fp32 [8]),
     posterior sample z = scale (mean + exp(0.5 clamp(logvar, -30, 20)) n_post), then sa z + sb n_fwd.  Output j uses image
-    j % B_img; n_post fp32 [B_img, 4, hh, ww], n_fwd fp32 [out_count, 4, hh, ww]."""
+    j % B_img; n_post fp32 [B_img, 4, hh, ww], n_fwd fp32 [out_count, 4, hh, ww].  ``with_z`` returns (x_t, z), z fp32
+    [B_img, 4, hh, ww] (af_vae_latents_z_q_sample, the same launch)."""
     _chk_f16(h, "vae_latents_q_sample.h")
     if h.dim() != 4 or h.shape[3] != 8:
         raise RuntimeError(f"vae_latents_q_sample: h must be [B, hh, ww, 8], got {tuple(h.shape)}")
@@ -1012,9 +1056,13 @@ def vae_latents_q_sample(h: torch.Tensor, qw: torch.Tensor, qb: torch.Tensor, n_
     if out_count <= 0 or out_count % B_img != 0:
         raise RuntimeError(f"vae_latents_q_sample: out_count {out_count} is not a positive multiple of the image count {B_img}")
     x_t = torch.empty((out_count, 4, hh, ww), dtype=torch.float32, device=h.device)
-    _lib.check(_lib.lib().af_vae_latents_q_sample(_p(h), _p(qw), _p(qb), _p(n_post), _p(n_fwd), float(scale), float(sa), float(sb),
-                                                  _p(x_t), B_img, out_count, hh, ww, _stream()), "af_vae_latents_q_sample")
-    return x_t
+    args = [_p(h), _p(qw), _p(qb), _p(n_post), _p(n_fwd), float(scale), float(sa), float(sb), _p(x_t)]
+    if not with_z:
+        _lib.check(_lib.lib().af_vae_latents_q_sample(*args, B_img, out_count, hh, ww, _stream()), "af_vae_latents_q_sample")
+        return x_t
+    z = torch.empty((B_img, 4, hh, ww), dtype=torch.float32, device=h.device)
+    _lib.check(_lib.lib().af_vae_latents_z_q_sample(*args, _p(z), B_img, out_count, hh, ww, _stream()), "af_vae_latents_z_q_sample")
+    return x_t, z
 
 
 # ----------------------------------------------------------------------------- backward ops

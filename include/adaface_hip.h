@@ -385,6 +385,23 @@ int af_cfg_dpmpp_step(const void* eps2, const void* x, const void* x_base, const
 int af_cfg_lcm_step(const void* eps2, const void* x, const void* noise, void* x_next, void* denoised, int64_t n, int has_uncond,
                     float guidance, float sqrt_a, float sqrt_1ma, float c_out, float c_skip, float sqrt_a_next, float sqrt_1ma_next,
                     void* stream);
+/* inpainting (INTEGRATION.md "Inpainting"): the three steps above with the mask blend as their tail, one launch each.  x_prev / x_out /
+ * x_next become m ? x_new : known per element of output b, channel c, pixel p, where x_new is what the plain step writes,
+ * m = mask[b % B_mask][p] (fp32 [B_mask,1,hw], binary: nonzero keeps x_new), z = z[b % B_img][c][p] (fp32 [B_img,4,hw]) and
+ * known = fma(sb_next, noise[b][c][p], sa_next z) (noise fp32 [n / (4 hw), 4, hw]), or known = z when noise is NULL (the last
+ * step; noise is not read).  pred_x0 / x0_out / denoised are not blended.  n % (4 hw) == 0, n < 2^31; 16-byte accesses when
+ * hw % 4 == 0 and every pointer is aligned.  The LCM step's own re-noising draw stays `noise`; the blend's is `blend_noise`.  */
+int af_cfg_ddim_inpaint_step(const void* eps2, const void* x, void* x_prev, void* pred_x0, int64_t n, int has_uncond, float guidance,
+                             float a_t, float a_prev, const void* z, const void* noise, const void* mask, int B_img, int B_mask,
+                             int64_t hw, float sa_next, float sb_next, void* stream);
+int af_cfg_dpmpp_inpaint_step(const void* eps2, const void* x, const void* x_base, const void* x0_prev, void* x_out, void* x0_out,
+                              int64_t n, int has_uncond, float guidance, float alpha_s, float sigma_s, float c_base, float c0, float c1,
+                              const void* z, const void* noise, const void* mask, int B_img, int B_mask, int64_t hw, float sa_next,
+                              float sb_next, void* stream);
+int af_cfg_lcm_inpaint_step(const void* eps2, const void* x, const void* noise, void* x_next, void* denoised, int64_t n, int has_uncond,
+                            float guidance, float sqrt_a, float sqrt_1ma, float c_out, float c_skip, float sqrt_a_next,
+                            float sqrt_1ma_next, const void* z, const void* blend_noise, const void* mask, int B_img, int B_mask,
+                            int64_t hw, float sa_next, float sb_next, void* stream);
 /* q_sample (ldm/models/diffusion/ddpm.py:395-398): x_t = sa[b] x0 + sb[b] noise, fp32, per-sample scalars */
 int af_q_sample(const void* x0, const void* noise, const void* sa, const void* sb, void* xt, int B, int64_t per,
                 void* stream);
@@ -398,6 +415,9 @@ int af_image_u8_to_nhwc_f16(const void* img, void* out, int B, int H, int W, voi
  * x_t = sa z + sb n_fwd, n_fwd / x_t fp32 NCHW [B_out,4,hh,ww]; output j reads image j % B_img.  B_out % B_img == 0.        */
 int af_vae_latents_q_sample(const void* h, const void* qw, const void* qb, const void* n_post, const void* n_fwd, float scale, float sa,
                             float sb, void* x_t, int B_img, int B_out, int hh, int ww, void* stream);
+/* the same, also writing the image latents z fp32 NCHW [B_img,4,hh,ww] (inpainting blends with them).  z must not be NULL.     */
+int af_vae_latents_z_q_sample(const void* h, const void* qw, const void* qb, const void* n_post, const void* n_fwd, float scale,
+                              float sa, float sb, void* x_t, void* z, int B_img, int B_out, int hh, int ww, void* stream);
 
 /* y = x * sigmoid(x), fp16 (nn.SiLU on the time embedding, openaimodel.py:219-220) */
 int af_silu_f16(const void* x, void* y, int64_t n, void* stream);
