@@ -35,6 +35,7 @@ EXPORTS = (
     "af_splitk_reduce", "af_groupnorm_splitk_ok", "af_groupnorm_splitk", "af_xattn_chain",
     "af_image_u8_to_nhwc_f16", "af_vae_latents_q_sample", "af_cfg_dpmpp_step", "af_cfg_lcm_step",
     "af_cfg_ddim_inpaint_step", "af_cfg_dpmpp_inpaint_step", "af_cfg_lcm_inpaint_step", "af_vae_latents_z_q_sample",
+    "af_vae_attention",
 )
 
 
@@ -164,6 +165,7 @@ def lib() -> C.CDLL:
     L.af_im2col3x3.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     L.af_softmax_rows.argtypes = [vp, vp, i64, i32, vp]
     L.af_mask_pairs.argtypes = [vp, vp, i32, vp]
+    L.af_vae_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.af_prefetch.argtypes = [vp, i64, vp]
     L.af_prefetch_ex.argtypes = [vp, i64, i32, vp]
     L.af_xattn_scores.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]

@@ -15,6 +15,11 @@ files or VAE weights, so every component can be passed in, and:
 * ``vae``: optional object with ``decode(latents / 0.18215) -> images in [-1, 1]`` (VAE decode is SURVEY.md 8f rank 3); without it
   ``forward`` returns the final latents ``[BS, 4, 64, 64]`` instead of PIL images.
 
+Image sizes (INTEGRATION.md "Image sizes"): all three pipelines take any image whose sides are multiples of 64 from 64 to 1024 pixels
+(latent sides multiples of 8 up to 128; ``text2img`` takes the size from ``noise``).  The VAE's attention layer runs fused
+(``af_vae_attention``) wherever its three-launch form does not apply, and ``_to_pil`` decodes in slices of images when a batch would pass the
+kernels' 32-bit activation bounds.  A larger side is a ValueError before any GPU work.
+
 ``pipeline_name="img2img"`` is the reference's img2img branch (diffusers' ``StableDiffusionImg2ImgPipeline`` with the DDIM scheduler,
 what ``adaface_translate.py`` runs): ``forward``'s first argument carries the input image(s) (one PIL image or a list of 1 or
 ``out_image_count``; see ``img2img_images_u8``), ``vae`` must be an ``AutoencoderKL`` (encoder + decoder), and ``ref_img_strength``
@@ -108,6 +113,9 @@ def inpaint_masks(mask_images, out_image_count, size):
             im = im.resize(tuple(size), resample=Image.LANCZOS)
         out.append(np.asarray(im, dtype=np.uint8)[::8, ::8] >= 128)
     return torch.from_numpy(np.stack(out)[:, None].astype(np.float32))
+
+
+MAX_IMAGE_SIDE = 1024      # pixels; the VAE (its fused attention layer, 16384 tokens) is built and tested up to a 128 x 128 latent
 
 
 # default_scheduler_name -> sampler class (a sampling.Sampler, as LCMSampler: sample / img2img_steps / sample_img2img)
@@ -427,9 +435,15 @@ class AdaFaceWrapper(nn.Module):
                 raise ValueError(f"the {self.pipeline_name} pipeline encodes its input images: it needs an AutoencoderKL (encoder + "
                                  f"decoder) as vae, got {type(self.vae).__name__ if self.vae is not None else None}")
             images_u8 = img2img_images_u8(noise, out_image_count)
+            if max(images_u8.shape[1:3]) > MAX_IMAGE_SIDE:
+                raise ValueError(f"{self.pipeline_name} input images may be at most {MAX_IMAGE_SIDE} pixels on a side (the VAE's limit), got "
+                                 f"{images_u8.shape[2]} x {images_u8.shape[1]}")
             if inpaint:
                 masks = inpaint_masks(mask_image, out_image_count, (images_u8.shape[2], images_u8.shape[1]))
             self._sampler().img2img_steps(self.num_inference_steps, ref_img_strength)    # refuse a bad strength before any work
+        elif self.vae is not None and torch.is_tensor(noise) and noise.dim() == 4 and max(noise.shape[2:]) * 8 > MAX_IMAGE_SIDE:
+            raise ValueError(f"text2img latents may be at most {MAX_IMAGE_SIDE // 8} on a side ({MAX_IMAGE_SIDE} pixels, the VAE's limit), got "
+                             f"noise of shape {tuple(noise.shape)}")
         if prompt_embeds is None:
             pe, ne, _, _ = self.encode_prompt(prompt, negative_prompt, placeholder_tokens_pos=placeholder_tokens_pos,
                                               ablate_prompt_only_placeholders=ablate_prompt_only_placeholders,
@@ -473,7 +487,10 @@ class AdaFaceWrapper(nn.Module):
         return LCMSampler(self.ldm) if self.use_lcm else SCHEDULERS[self.default_scheduler_name](self.ldm)
 
     def _to_pil(self, latents):
-        images = self.vae.decode(latents / 0.18215)
+        # decode in slices of images that keep the widest activation (256 channels at full resolution) below 2^31 elements, the bound of the
+        # kernels' 32-bit offsets: 8 images at 1024 x 1024, 32 at 512 x 512 -- one slice for every batch the pipelines run by default
+        per = max(1, (2 ** 31 - 1) // (latents.shape[2] * latents.shape[3] * 64 * 256))
+        images = torch.cat([self.vae.decode(latents[i:i + per] / 0.18215) for i in range(0, latents.shape[0], per)])
         images = ((images.float() / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
         from PIL import Image
         return [Image.fromarray(im) for im in images]

@@ -9,7 +9,10 @@ keys load with ``load_state_dict``.
 Execution is NHWC fp16 through the C ABI, with the kernels the U-Net already uses: GroupNorm(32, eps 1e-6)+swish fused, 3x3 convs as
 implicit GEMM (the nearest x2 upsample folded into the following conv's gather, the residual / 1x1 ``nin_shortcut`` in the epilogue), and
 the one attention layer (single head, 512 channels, 4096 tokens at 512x512) as  q.k^T GEMM -> ``af_softmax_rows`` -> P.v GEMM per
-image: its head dim is beyond the flash kernel's register budget and the layer is ~2 % of the decoder.
+image wherever that form applies (tokens % 128 == 0 and <= 4096: the row softmax holds 4096 keys and the GEMM operands are whole tiles), and as
+the fused ``af_vae_attention`` (online softmax, no [N, N] matrix; head dim 128 or 512, any token count % 8 == 0 up to 16384 = a 1024x1024 image)
+everywhere else; ``AF_VAE_FLASH=1`` sends every mask-free inference call the fused kernel takes to it (``vae_attention_path`` is the rule).  The
+head dim is beyond ``af_attention``'s register budget (d <= 160), so the fused kernel splits a query block's channels over a workgroup's waves.
 
 The weights are frozen, but the ArcFace alignment terms differentiate through the decoder into the latent
 (``decode_first_stage_with_grad``, ddpm.py:899-908 -> ``calc_arcface_align_loss``, ddpm.py:2511-2535), so ``decode`` of a latent that
@@ -17,6 +20,8 @@ requires grad is a ``torch.autograd`` node (``VAEDecodeFn``) with the INPUT grad
 keeps the GroupNorm inputs + statistics) and ``hip_bwd`` (``af_groupnorm_bwd``, the flipped-weight dgrad convolutions -- a folded nearest
 x2 upsample becomes ``af_sumpool2x2`` of the dgrad --, and for the attention layer the explicit P recomputed, ``af_softmax_rows_bwd`` and
 four GEMMs per image).  No parameter gradient is formed."""
+import os
+
 import torch
 import torch.nn as nn
 
@@ -110,6 +115,29 @@ class ResnetBlock(nn.Module):
         return self.norm1.hip_bwd(x, st1, self.conv1.hip_dgrad(dh), silu=True, add=dxs)
 
 
+def vae_attention_path(N, C, masked=False, train=False, flash_env=False):
+    """Which form the VAE's attention layer takes over N tokens of C channels: "gemm" (q.k^T GEMM -> af_softmax_rows -> P.v GEMM per image, the
+    [N, N] matrix in memory) or "flash" (af_vae_attention).  Every call the GEMM form accepts keeps it -- tokens % 128 == 0 and <= 4096, C % 128 == 0,
+    and always with the fg / aug pair mask (``masked``) or on the decode-with-grad path (``train``), whose backward recomputes P in that form --
+    unless ``flash_env`` (AF_VAE_FLASH=1) asks for the fused kernel wherever it applies: mask-free inference, C in ops.VAE_ATTN_DIMS,
+    tokens % 8 == 0 and <= ops.VAE_ATTN_MAX_TOKENS.  A mask-free inference call the GEMM form refuses goes to the fused kernel; what neither
+    takes raises NotImplementedError."""
+    gemm_ok = 0 < N <= 4096 and N % 128 == 0 and C % 128 == 0
+    flash_ok = 0 < N <= ops.VAE_ATTN_MAX_TOKENS and N % 8 == 0 and C in ops.VAE_ATTN_DIMS
+    if masked or train:
+        if gemm_ok:
+            return "gemm"
+        raise NotImplementedError(f"VAE attention over {N} tokens of {C} channels {'with the fg / aug pair mask' if masked else 'with a backward'}: this form runs "
+                                  "as q.k^T GEMM -> af_softmax_rows -> P.v GEMM only, which takes tokens % 128 == 0 up to 4096 and C % 128 == 0 "
+                                  "(af_vae_attention takes other sizes, but neither the mask nor the backward)")
+    if flash_ok and (flash_env or not gemm_ok):
+        return "flash"
+    if gemm_ok:
+        return "gemm"
+    raise NotImplementedError(f"VAE attention over {N} tokens of {C} channels: af_vae_attention takes C in {ops.VAE_ATTN_DIMS} and tokens % 8 == 0 up to "
+                              f"{ops.VAE_ATTN_MAX_TOKENS}; the GEMM + af_softmax_rows form takes tokens % 128 == 0 up to 4096 and C % 128 == 0")
+
+
 class AttnBlock(nn.Module):
     def __init__(self, in_channels):
         super().__init__()
@@ -145,28 +173,27 @@ class AttnBlock(nn.Module):
         cls = (fg * aug != 0).to(torch.uint8) + 2 * ((1 - fg) * aug != 0).to(torch.uint8)
         return cls.reshape(cls.shape[0], H * W).to(torch.uint8).contiguous()
 
-    def hip(self, x, mask=None):
+    def hip(self, x, mask=None, _train=False):
         B, H, W, C = x.shape
         N = H * W
         cls = self.pair_classes(mask, H, W)
-        if N % 8 != 0 or N > 4096:
-            raise NotImplementedError(f"VAE attention over {N} tokens (af_softmax_rows holds rows up to 4096)")
+        path = vae_attention_path(N, C, masked=cls is not None, train=_train, flash_env=os.environ.get("AF_VAE_FLASH") == "1")
         hn = self.norm.hip(x).reshape(B * N, C)
         q = ops.gemm(hn, self._q_scaled_pack())
         k = ops.gemm(hn, self.k.packed())
         v = ops.gemm(hn, self.v.packed())
-        vt = ops.transpose_tokens(v, B, N, C, C)                                  # [B, C, N]: the P.v GEMM's K-contiguous operand
-        kp, cp = ops.round_up(C, 64), ops.round_up(C, 128)
-        if kp != C or N % 128 != 0 or vt.shape[2] % 64 != 0 or cp != C:
-            raise NotImplementedError("VAE attention operands must already be tile aligned (C % 128 == 0, tokens % 128 == 0)")
-        out = torch.empty((B * N, C), dtype=F16, device=x.device)
-        for b in range(B):                                                        # one image at a time: [N, N] scores = 32 MB at 64x64
-            kb = ops.PackedWeight(k[b * N:(b + 1) * N], None, N, C, C, 1, C)      # keys as the "weight" [N, C], K-contiguous
-            p = ops.softmax_rows(ops.gemm(q[b * N:(b + 1) * N], kb))
-            if cls is not None:
-                ops.mask_pairs_(p, cls[b].to(x.device))
-            vb = ops.PackedWeight(vt[b], None, C, N, N, 1, N)                     # V^T [C, N]
-            out[b * N:(b + 1) * N] = ops.gemm(p, vb)
+        if path == "flash":
+            out = ops.vae_attention(q, k, v, B=B, N=N, C=C)
+        else:
+            vt = ops.transpose_tokens(v, B, N, C, C)                              # [B, C, N]: the P.v GEMM's K-contiguous operand
+            out = torch.empty((B * N, C), dtype=F16, device=x.device)
+            for b in range(B):                                                    # one image at a time: [N, N] scores = 32 MB at 64x64
+                kb = ops.PackedWeight(k[b * N:(b + 1) * N], None, N, C, C, 1, C)  # keys as the "weight" [N, C], K-contiguous
+                p = ops.softmax_rows(ops.gemm(q[b * N:(b + 1) * N], kb))
+                if cls is not None:
+                    ops.mask_pairs_(p, cls[b].to(x.device))
+                vb = ops.PackedWeight(vt[b], None, C, N, N, 1, N)                 # V^T [C, N]
+                out[b * N:(b + 1) * N] = ops.gemm(p, vb)
         y = ops.gemm(out, self.proj_out.packed(), residual=x.reshape(B * N, C))
         return y.reshape(B, H, W, C)
 
@@ -183,7 +210,7 @@ class AttnBlock(nn.Module):
             raise NotImplementedError("the masked AttnBlock belongs to the encoder, which is never differentiated")
         B, H, W, C = x.shape
         hn, st = self.norm.hip_train(x)
-        return self.hip(x), (x, st, hn.reshape(B * H * W, C))
+        return self.hip(x, _train=True), (x, st, hn.reshape(B * H * W, C))
 
     def hip_bwd(self, saved, dy):
         """Per image: P recomputed (q.k^T GEMM + row softmax), dV = P^T dO, dP = dO V^T, dS = softmax_bwd(P, dP), dQ = dS K, dK = dS^T Q;

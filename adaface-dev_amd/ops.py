@@ -1224,6 +1224,25 @@ def softmax_rows(x):
     return y
 
 
+VAE_ATTN_DIMS = (128, 512)          # head dims af_vae_attention is built for: the mid width of the reduced test VAE and of SD-1.5's
+VAE_ATTN_MAX_TOKENS = 16384         # a 128 x 128 latent (1024 x 1024 image): the range the kernel is tested over
+
+
+def vae_attention(q, k, v, *, B: int, N: int, C: int):
+    """Fused single-head attention of the VAE's attention layer: q, k, v [B*N, C] fp16 token rows (column slices of wider buffers are fine), the
+    C^-0.5 scale already in q -> softmax(q k^T) v [B*N, C].  Online softmax in one launch, no [N, N] matrix; any N % 8 == 0.  The kernel reads
+    the values key-contiguous, so v is transposed first ([B, C, N], 2 N C bytes: noise beside the 4 N^2 C FLOP)."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        _chk_f16_rows(t, f"vae_attention.{name}")
+        if t.shape[0] != B * N or t.shape[1] != C:
+            raise RuntimeError(f"vae_attention.{name}: expected [{B * N}, {C}], got {tuple(t.shape)}")
+    vt = transpose_tokens(v, B, N, C, _ld(v))
+    o = torch.empty((B * N, C), dtype=F16, device=q.device)
+    rc = _lib.lib().af_vae_attention(_p(q), _p(k), _p(vt), _p(o), B, N, C, _ld(q), _ld(k), vt.stride(1), C, _stream())
+    _lib.check(rc, "af_vae_attention")
+    return o
+
+
 def softmax_rows_bwd(p, dp):
     """ds = p * (dp - rowsum(p * dp)) for fp16 [rows, L] probabilities and their gradient."""
     _chk_f16(p, "softmax_rows_bwd.p")

@@ -475,6 +475,13 @@ int af_clamp_f32(void* a, float lo, float hi, int64_t n, void* stream);
 /* ---- VAE decoder (ldm/modules/diffusionmodules/model.py:151-243 AttnBlock): row softmax of an explicit fp16 score matrix
  * [rows, L], L % 8 == 0, L <= 4096 (single-head 512-dim attention runs as af_gemm -> af_softmax_rows -> af_gemm) */
 int af_softmax_rows(const void* x, void* y, int64_t rows, int L, void* stream);
+/* The same layer fused, at any size: o = softmax(q k^T) v for ONE head of dim C in {128, 512} with online softmax -- no [N, N] matrix and no
+ * workspace, memory is O(N C).  q, k [B*N, ldq / ldk] fp16 token rows (the C^-0.5 scale already folded into q), vt [B, C, ldv] the values
+ * TRANSPOSED with the key index contiguous (af_transpose_tokens; ldv >= N), o [B*N, ldo].  N % 8 == 0, any N >= 8 (query and key tails are
+ * handled; keys >= N and the ldv pad are never read as data); strides multiples of 8, operands 16-byte aligned.  fp32 scores, fp32 running
+ * reference / sum and fp32 accumulation; P is rounded to fp16 as the MFMA operand.  AF_E_UNSUPPORTED for another C and for an operand of 2^31
+ * elements or more (offsets are not wrapped).                                                                                             */
+int af_vae_attention(const void* q, const void* k, const void* vt, void* o, int B, int N, int C, int ldq, int ldk, int ldv, int ldo, void* stream);
 /* its backward, ds = p * (dp - rowsum(p * dp)), for the decode-with-grad path of the ArcFace alignment loss (ddpm.py:2511-2535
  * differentiates through decode_first_stage_with_grad, ddpm.py:899-908) */
 int af_softmax_rows_bwd(const void* p, const void* dp, void* ds, int64_t rows, int L, void* stream);
