@@ -1781,7 +1781,9 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
   gemm3_epilogue<E3_STD, NWM, NWN, TN, CH_LDS, PATCH>(p, acc, af_smem, tile_m, tile_n, wm, wn, fr, fq, tid);
 }
 
-// scope of the halo-resident kernel
+// scope of the halo-resident kernel, stated here only: af_gemm3_try_launch launches on it and ops.conv_halo_eligible asks it through af_gemm_halo_variant.
+// It reads shape and mode fields, no operand pointer, so a host-side descriptor gets the answer of a launch (af_gemm has refused a K tail without a3 / a4
+// before it gets here).
 // 0 = outside; 1 = the 256 x 160 tile on whole image rows (the U-Net's levels); 2 = the 256 x 128 tile on whole image rows; 3 = the 256 x 128 tile on
 // 16 x 16-pixel patches (images wider than 64 pixels: the VAE decoder's 128 / 256 / 512 levels)
 static int conv3h_variant(const af_gemm_desc* d) {
@@ -1789,7 +1791,7 @@ static int conv3h_variant(const af_gemm_desc* d) {
   const bool n160 = d->N % CH_BN == 0;
   if (!n160 && d->N % 128 != 0) return 0;
   if (d->c3 || d->c4) {                                            // K tail (round 6): plain rows of a3 | a4 on the output grid, whole 64-column stages
-    if (!n160 || d->c3 <= 0 || d->c3 % 64 != 0 || d->c4 < 0 || d->c4 % 64 != 0 || d->a3 == nullptr || (d->c4 > 0 && d->a4 == nullptr) || d->upsample) return 0;
+    if (!n160 || d->c3 <= 0 || d->c3 % 64 != 0 || d->c4 < 0 || d->c4 % 64 != 0 || d->upsample) return 0;
     if ((long)d->M * std::max(d->lda3 ? d->lda3 : d->c3, d->lda4 ? d->lda4 : d->c4) * 2 >= (1L << 32)) return 0;
     if ((long)d->B * d->H * d->W >= (1L << 24)) return 0;        // the tail form's halo gather multiplies pixel indices with __umul24
   }
@@ -1799,8 +1801,8 @@ static int conv3h_variant(const af_gemm_desc* d) {
   if (d->act == AF_ACT_GEGLU || d->out_mode == AF_OUT_SPLIT_T || d->ln_colsum != nullptr || d->kpad % 64 != 0) return 0;
   if ((long)d->B * d->H * d->W * std::max(d->c1, d->c2) * 2 >= (1L << 32)) return 0;      // the halo gather's 32-bit byte offsets
   if ((long)((d->N + 127) / 128 * 128) * d->kpad * 2 >= (1L << 32)) return 0;                // ... and the weight pieces' (w_off)
-  if (d->Wo > 64) {                                                // patches: no K tail, no split-K (the caller checks), no 160-wide form
-    if (n160 || d->Wo % 16 != 0 || d->Ho % 16 != 0 || d->c3 || d->c4) return 0;
+  if (d->Wo > 64) {                                                // patches: no K tail, no split-K, no 160-wide form
+    if (n160 || d->Wo % 16 != 0 || d->Ho % 16 != 0 || d->c3 || d->c4 || d->splits > 1) return 0;
     return 3;
   }
   if (d->Wo != 8 && d->Wo != 16 && d->Wo != 32 && d->Wo != 64) return 0;
@@ -1809,7 +1811,6 @@ static int conv3h_variant(const af_gemm_desc* d) {
   if (d->Ho < rows && (rows / d->Ho) * (d->Ho + 2) * (d->Wo + 2) > CH_NP_MAX * 8) return 0;     // the images' halo blocks must fit one halo buffer
   return n160 ? 1 : 2;
 }
-static bool conv3h_eligible(const af_gemm_desc* d) { return conv3h_variant(d) != 0; }
 
 static int conv3h_chunks(const af_gemm_desc* d) { return (d->c1 + d->c2) / 64; }
 
@@ -2189,7 +2190,6 @@ int af_gemm3_try_launch(const af_gemm_desc* d, int splits, int wide, hipStream_t
   const int halo_variant = wide == 11 ? conv3h_variant(d) : 0;
   if (wide == 11 && halo_variant == 0) return 1;                // halo-resident 3x3 kernel (tile 14)
   if (halo_r5 && (d->c3 > 0 || halo_variant != 1)) return 1;    // (the K tail and the 256 x 128 forms exist in the round-6 loop only)
-  if (halo_variant == 3 && splits > 1) return 1;                // (patches: never split)
   if (d->upsample && !((wide == 4 || wide == 5 || (wide >= 8 && wide <= 12)) && d->upsample == 1 && d->taps == 9)) return 1;   // nearest x2: whole-line kernel only
   if (d->c1 % BK3 != 0 || d->c2 % BK3 != 0 || d->zeros == nullptr) return 1;
   if (d->c3 > 0 && (wide < 4 || (wide > 10 && wide != 12 && wide != 11) || d->taps != 9 || d->upsample || (d->stride != 0 && d->stride != 1))) return 1;   // K tail: whole-line tap-by-tap tiles + the halo-resident kernel
@@ -2351,7 +2351,7 @@ int af_gemm3_try_launch(const af_gemm_desc* d, int splits, int wide, hipStream_t
 
 int af_gemm3_effective_splits(const af_gemm_desc* d, int splits, int wide) {
   if (wide == 16) wide = 11;                                     // tile 19 = tile 14's scope
-  const int nk = (wide == 11 && conv3h_eligible(d)) ? conv3h_chunks(d) : d->kpad / (wide >= 4 ? 64 : BK3);
+  const int nk = (wide == 11 && conv3h_variant(d) != 0) ? conv3h_chunks(d) : d->kpad / (wide >= 4 ? 64 : BK3);
   int s = splits > 1 ? splits : 1;
   if (s > nk) s = nk;
   const int per = (nk + s - 1) / s;

@@ -168,35 +168,12 @@ import os as _os
 _TUNE_PATH = _os.environ.get("AF_TUNE_TABLE") or _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "tuning", "gfx950_gemm.json")
 _tune_table = None
 def conv_halo_eligible(d) -> bool:
-    """The scope of af_gemm tile 14, the halo-resident 3x3 kernel (include/adaface_hip.h); tools/autotune_gemm.py times it against the
-    tap-by-tap tiles wherever this holds.  Three forms (csrc/af_gemm3.hip::conv3h_variant): 256 x 160 tiles on whole image rows (the U-Net's levels,
-    with the K-concatenated shortcut since round 6), 256 x 128 tiles on whole rows, and 256 x 128 tiles on 16 x 16-pixel patches of images wider
-    than 64 pixels (the VAE's 128 / 256 / 512 levels)."""
-    up = 2 if d.upsample else 1
-    tail = d.c3 > 0 or d.c4 > 0
-    n160 = d.N % 160 == 0
-    if not (d.taps == 9 and d.stride in (0, 1) and d.upsample in (0, 1) and not d.tap_shift and d.c1 % 64 == 0 and d.c2 % 64 == 0
-            and (n160 or d.N % 128 == 0) and d.M % 256 == 0 and d.Ho == up * d.H and d.Wo == up * d.W and d.act != AF_ACT_GEGLU
-            and d.out_mode == AF_OUT_NORMAL):
-        return False
-    if tail and not (n160 and d.c3 > 0 and d.c3 % 64 == 0 and d.c4 % 64 == 0 and not d.upsample):     # round 6: the K-concatenated 1x1 shortcut
-        return False
-    # the kernel's 32-bit address arithmetic (conv3h_variant): the halo gather's byte offsets, the tail form's __umul24 pixel indices, the weight offsets
-    if d.B * d.H * d.W * max(d.c1, d.c2) * 2 >= 1 << 32 or (tail and d.B * d.H * d.W >= 1 << 24) or round_up(d.N, 128) * d.kpad * 2 >= 1 << 32:
-        return False
-    if tail and d.M * max(d.lda3 or d.c3, d.lda4 or d.c4) * 2 >= 1 << 32:
-        return False
-    if d.Wo > 64:
-        return not n160 and not tail and d.Wo % 16 == 0 and d.Ho % 16 == 0 and d.splits <= 1
-    return d.Wo in (8, 16, 32, 64) and _halo_rows_ok(d.Ho, d.Wo)
-
-
-def _halo_rows_ok(Ho: int, Wo: int) -> bool:
-    """A tile of the halo-resident kernel is 256 output pixels: whole rows of one image, or -- at the 8 x 8 level -- whole images whose halo blocks fit its 400-pixel buffer."""
-    rows = 256 // Wo
-    if Ho % rows == 0:
-        return True
-    return rows % Ho == 0 and (rows // Ho) * (Ho + 2) * (Wo + 2) <= 400
+    """Whether af_gemm runs descriptor ``d`` on the halo-resident 3x3 kernel when asked for tile 14 / 19 -- the library's own launch predicate
+    (af_gemm_halo_variant, csrc/af_gemm3.hip::conv3h_variant; no launch, operand pointers are not read).  The table's key carries no image
+    geometry, so a tabled or default tile 14 can meet a latent outside that scope (W not 8 / 16 / 32 / 64, ragged rows, ...); the library then
+    falls back to the register-staged kernel, which writes no GroupNorm statistics and has no K tail.  Every caller that depends on the kernel
+    really running asks here: _launch_gemm (VAE_HALO_DEFAULT, producer statistics), conv3x3 (K tail), tools/autotune_gemm.py, the tuned-shape tests."""
+    return _lib.lib().af_gemm_halo_variant(C.byref(d)) != 0
 
 
 _tune_recorder = None      # set by tools/autotune_gemm.py: callable(key, desc, device) -> (tile, splits)
@@ -285,6 +262,11 @@ class GnPartials:
     def __init__(self, ws, nblk, cpg, B, hw, C):
         self.ws, self.nblk, self.cpg, self.B, self.hw, self.C = ws, nblk, cpg, B, hw, C
         self.ptr, self.version = 0, -1
+
+    @classmethod
+    def alloc(cls, device, B: int, hw: int, C: int, cpg: int) -> "GnPartials":
+        """The workspace a producing launch fills for B images of hw rows (128-row blocks) x C channels in groups of cpg: [B][128 blocks][32 groups][sum, sumsq]."""
+        return cls(torch.empty((B, 128, 32, 2), dtype=torch.float32, device=device), hw // 128, cpg, B, hw, C)
 
     def attach(self, t: torch.Tensor) -> torch.Tensor:
         self.ptr, self.version = t.data_ptr(), t._version
@@ -454,14 +436,10 @@ def _launch_gemm(d: "GemmDesc", device, what: str, tile: int = 0, splits: int = 
     gn = None
     if gn_cpg and GN_FROM_PRODUCER and _tune_recorder is None:
         rpb = d.rows_per_batch if d.rows_per_batch > 0 else d.M
-        # the table's key carries no image geometry: tile 14 (halo-resident 3x3) on a latent outside its scope (W not 16 / 32 / 64, ragged rows)
-        # falls back to a tap-by-tap tile INSIDE the library, which leaves no statistics -- ask for them only where tile 14 will really run
         if (d.tile not in (14, 19) or conv_halo_eligible(d)) and d.M % rpb == 0 and d.ld_out in (0, d.N) \
                 and _lib.lib().af_gemm_gn_stats_ok(d.tile, d.splits, d.taps, d.act, d.out_mode, d.N, gn_cpg, rpb) == 1:
-            nb = d.M // rpb
-            ws = torch.empty((nb, 128, 32, 2), dtype=torch.float32, device=device)
-            d.gn_partials, d.gn_cpg = ws.data_ptr(), gn_cpg
-            gn = GnPartials(ws, rpb // 128, gn_cpg, nb, rpb, d.N)
+            gn = GnPartials.alloc(device, d.M // rpb, rpb, d.N, gn_cpg)
+            d.gn_partials, d.gn_cpg = gn.ws.data_ptr(), gn_cpg
     if _weight_prefetcher is not None and _weight_prefetcher.mode is not None:
         _weight_prefetcher.note(int(d.wt), int(d.kpad) * round_up(int(d.N), 128) * 2)
     left = None
@@ -538,9 +516,14 @@ def conv3x3_skip_tile(M: int, N: int, cin: int, ktail: int):
     else what the table says for the plain convolution of the same shape (the tail only lengthens K), else a whole-line default."""
     for K in (9 * cin + ktail, 9 * cin):
         t = tune_table().get(f"9,{M},{N},{K},0,0,1,0")
-        if t is not None and 7 <= t[0] <= 14:          # (14: the halo-resident kernel takes the tail since round 6; conv3x3 falls back inside the library outside its scope)
+        if t is not None and 7 <= t[0] <= 14:          # (14: the halo-resident kernel takes the tail since round 6; outside its scope conv3x3 takes _whole_line_tile)
             return t
-    return (7 if (N % 320 == 0 and M >= 8192) else (11 if N % 160 == 0 else 8)), 1
+    return _whole_line_tile(M, N), 1
+
+
+def _whole_line_tile(M: int, N: int) -> int:
+    """The whole-line tap-by-tap tile for a 3x3 convolution the table has no (usable) entry for: 128 x 320, 128 x 160 or 128 x 128."""
+    return 7 if (N % 320 == 0 and M >= 8192) else (11 if N % 160 == 0 else 8)
 
 
 def conv3x3(x: torch.Tensor, pw: PackedWeight, *, x2: Optional[torch.Tensor] = None, stride: int = 1, upsample: bool = False,
@@ -592,9 +575,7 @@ def conv3x3(x: torch.Tensor, pw: PackedWeight, *, x2: Optional[torch.Tensor] = N
         if tile == 0 and splits == 0 and _tune_recorder is None:
             tile, splits = conv3x3_skip_tile(d.M, d.N, c1 + c2, pw.k_tail)
             if tile == 14 and not conv_halo_eligible(d):
-                # the table's key has no image geometry: tile 14 on a latent outside its scope (W not 8 / 16 / 32 / 64, ragged rows) would fall back to
-                # the register-staged kernel inside the library, which has no K tail -- take a whole-line tap-by-tap tile instead
-                tile, splits = (7 if (d.N % 320 == 0 and d.M >= 8192) else (11 if d.N % 160 == 0 else 8)), 1
+                tile, splits = _whole_line_tile(d.M, d.N), 1          # (the kernel tile 14 falls back to has no K tail)
     gn = _launch_gemm(d, x.device, "af_gemm(conv3x3)", tile, splits, gn_cpg=gn_cpg,
                       defer_gn=(out, pw.bias, rowbias, residual) if defer_gn else None)
     if gn is not None:
@@ -632,9 +613,8 @@ def ff_chain(x2d: torch.Tensor, pw1: PackedWeight, pw2: PackedWeight, residual: 
     out = torch.empty((M, Cn), dtype=F16, device=x2d.device)
     gn, gnp = None, None
     if gn_cpg and GN_FROM_PRODUCER and gn_cpg % 2 == 0 and Cn % gn_cpg == 0 and Cn // gn_cpg <= 32 and rows_per_batch % 128 == 0 and rows_per_batch // 128 <= 128:
-        nb = M // rows_per_batch
-        ws = torch.empty((nb, 128, 32, 2), dtype=torch.float32, device=x2d.device)
-        gn, gnp = GnPartials(ws, rows_per_batch // 128, gn_cpg, nb, rows_per_batch, Cn), ws.data_ptr()
+        gn = GnPartials.alloc(x2d.device, M // rows_per_batch, rows_per_batch, Cn, gn_cpg)
+        gnp = gn.ws.data_ptr()
     _pf_note(pw1.wt, pw2.wt, pw_p.wt)
     rc = _lib.lib().af_ff_chain(_p(x2d), _p(pw1.wt), _p(pw1.bias), _p(pw1.ln_cs), float(pw1.ln_eps), pw1.kpad, _p(pw2.wt), _p(pw2.bias), pw2.kpad, _p(residual),
                                 _p(pw_p.wt), _p(pw_p.bias), pw_p.kpad, _p(x_in), _p(out), gnp, int(gn_cpg if gn is not None else 0), int(rows_per_batch), M, Cn, pw2.K,
@@ -719,9 +699,9 @@ def _groupnorm_splitk(pr, x, gamma, beta, y, stats, B, hw, c, groups, eps, silu)
     return True
 
 
-def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, silu: bool, *,
-              x2: Optional[torch.Tensor] = None, groups: int = 32) -> torch.Tensor:
-    """x [B, ..., C1] (+ x2 [B, ..., C2]) -> [B, ..., C1+C2] fp16; gamma/beta fp32 [C1+C2]."""
+def _groupnorm(x, gamma, beta, eps, silu, x2, groups, want_stats: bool):
+    """groupnorm / groupnorm_train: one launch, chosen by what x's producer left -- its split-K slabs (PendingReduce), its partial statistics
+    (GnPartials), or nothing (a statistics pass).  Returns (y, stats); stats is None unless want_stats."""
     _chk_f16_raw(x, "groupnorm.x")               # (not _chk_f16: x may be the tensor whose reduce pass this GroupNorm is about to absorb)
     B, c1 = x.shape[0], x.shape[-1]
     hw = x.numel() // (B * c1)
@@ -730,21 +710,36 @@ def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
         _chk_f16(x2, "groupnorm.x2")
         c2 = x2.shape[-1]
     y = torch.empty(tuple(x.shape[:-1]) + (c1 + c2,), dtype=F16, device=x.device)
+    stats = torch.empty((B, groups, 2), dtype=torch.float32, device=x.device) if want_stats else None
     if _pending:
         pr = _take_pending(x, B, hw, c1) if x2 is None else flush_pending(x.device)
-        if pr is not None and _groupnorm_splitk(pr, x, gamma, beta, y, None, B, hw, c1, groups, eps, silu):
-            return y
+        if pr is not None and _groupnorm_splitk(pr, x, gamma, beta, y, stats, B, hw, c1, groups, eps, silu):
+            return y, stats
     gn = partials_of(x) if x2 is None else None
     if gn is not None and gn.B == B and gn.hw == hw and gn.C == c1 and gn.cpg * groups == c1 and x.is_contiguous():
         # the launch that produced x left its partial statistics: normalise in one pass, no statistics pass (af_groupnorm_apply)
-        rc = _lib.lib().af_groupnorm_apply(_p(x), c1, _p(gamma), _p(beta), _p(y), None, B, hw, groups, float(eps), int(silu), _p(gn.ws), gn.nblk, _stream())
+        rc = _lib.lib().af_groupnorm_apply(_p(x), c1, _p(gamma), _p(beta), _p(y), _p(stats), B, hw, groups, float(eps), int(silu), _p(gn.ws), gn.nblk, _stream())
         _lib.check(rc, "af_groupnorm_apply")
-        return y
+        return y, stats
     ws = _gn_workspace(x.device, B)
-    rc = _lib.lib().af_groupnorm(_p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(y), B, hw, groups, float(eps), int(silu),
-                                 _p(ws), _stream())
-    _lib.check(rc, "af_groupnorm")
-    return y
+    if stats is None:
+        rc = _lib.lib().af_groupnorm(_p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(y), B, hw, groups, float(eps), int(silu), _p(ws), _stream())
+        _lib.check(rc, "af_groupnorm")
+    else:
+        rc = _lib.lib().af_groupnorm_stats(_p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(y), _p(stats), B, hw, groups, float(eps), int(silu), _p(ws), _stream())
+        _lib.check(rc, "af_groupnorm_stats")
+    return y, stats
+
+
+def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, silu: bool, *,
+              x2: Optional[torch.Tensor] = None, groups: int = 32) -> torch.Tensor:
+    """x [B, ..., C1] (+ x2 [B, ..., C2]) -> [B, ..., C1+C2] fp16; gamma/beta fp32 [C1+C2]."""
+    return _groupnorm(x, gamma, beta, eps, silu, x2, groups, False)[0]
+
+
+def groupnorm_train(x, gamma, beta, eps, silu, *, x2=None, groups=32):
+    """groupnorm() that also returns the (mean, rstd) statistics fp32 [B, groups, 2] for the backward."""
+    return _groupnorm(x, gamma, beta, eps, silu, x2, groups, True)
 
 
 def gn_proj_fused(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, pw: PackedWeight, groups: int = 32) -> Optional[torch.Tensor]:
@@ -1066,29 +1061,6 @@ def vae_latents_q_sample(h: torch.Tensor, qw: torch.Tensor, qb: torch.Tensor, n_
 
 
 # ----------------------------------------------------------------------------- backward ops
-def groupnorm_train(x, gamma, beta, eps, silu, *, x2=None, groups=32):
-    """groupnorm() that also returns the (mean, rstd) statistics fp32 [B, groups, 2] for the backward."""
-    _chk_f16_raw(x, "groupnorm.x")
-    B, c1 = x.shape[0], x.shape[-1]
-    hw = x.numel() // (B * c1)
-    c2 = 0 if x2 is None else x2.shape[-1]
-    y = torch.empty(tuple(x.shape[:-1]) + (c1 + c2,), dtype=F16, device=x.device)
-    stats = torch.empty((B, groups, 2), dtype=torch.float32, device=x.device)
-    if _pending:
-        pr = _take_pending(x, B, hw, c1) if x2 is None else flush_pending(x.device)
-        if pr is not None and _groupnorm_splitk(pr, x, gamma, beta, y, stats, B, hw, c1, groups, eps, silu):
-            return y, stats
-    gn = partials_of(x) if x2 is None else None
-    if gn is not None and gn.B == B and gn.hw == hw and gn.C == c1 and gn.cpg * groups == c1 and x.is_contiguous():
-        rc = _lib.lib().af_groupnorm_apply(_p(x), c1, _p(gamma), _p(beta), _p(y), _p(stats), B, hw, groups, float(eps), int(silu), _p(gn.ws), gn.nblk, _stream())
-        _lib.check(rc, "af_groupnorm_apply")
-        return y, stats
-    rc = _lib.lib().af_groupnorm_stats(_p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(y), _p(stats), B, hw, groups, float(eps),
-                                       int(silu), _p(_gn_workspace(x.device, B)), _stream())
-    _lib.check(rc, "af_groupnorm_stats")
-    return y, stats
-
-
 def groupnorm_bwd(x, gamma, beta, stats, dy, silu, *, x2=None, add=None, groups=32):
     """Input gradient of groupnorm(+SiLU): returns dx (or (dx1, dx2) when x2 is given)."""
     B, c1 = x.shape[0], x.shape[-1]

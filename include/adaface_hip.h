@@ -277,8 +277,10 @@ int af_groupnorm_splitk(const void* slabs, int splits, const void* bias, const v
 /* 1 when af_gemm with this (tile, splits) takes gn_partials for an output of N channels in groups of cpg and rows_per_batch rows per batch item */
 int af_gemm_gn_stats_ok(int tile, int splits, int taps, int act, int out_mode, int N, int cpg, int rows_per_batch);
 /* Which form of the halo-resident 3x3 kernel (tile 14) this descriptor would run: 0 = outside its scope (af_gemm falls back to a tap-by-tap tile),
- * 1 = 256 x 160 tiles on whole image rows, 2 = 256 x 128 tiles on whole image rows, 3 = 256 x 128 tiles on 16 x 16-pixel patches.  Reads the geometry
- * fields only (taps, c1 .. c4, N, B, H, W, Ho, Wo, stride, upsample, tap_shift, act, out_mode, kpad, M); no launch. */
+ * 1 = 256 x 160 tiles on whole image rows, 2 = 256 x 128 tiles on whole image rows, 3 = 256 x 128 tiles on 16 x 16-pixel patches.  This is the
+ * predicate af_gemm itself launches on, and the only statement of that scope: callers ask it instead of repeating it.  Reads the shape and mode fields
+ * only (taps, c1 .. c4, lda3, lda4, N, M, kpad, B, H, W, Ho, Wo, stride, upsample, tap_shift, act, out_mode, splits, and whether ln_colsum is set), no
+ * operand pointer, so a host-side descriptor without operands gets the answer of the real launch; no launch. */
 int af_gemm_halo_variant(const af_gemm_desc* d);
 int af_groupnorm(const void* x1, const void* x2, int c1, int c2, const void* gamma, const void* beta,
                  void* y, int B, int HW, int groups, float eps, int silu, void* workspace, void* stream);

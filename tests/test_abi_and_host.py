@@ -51,6 +51,24 @@ def test_bad_arguments_return_codes_without_a_gpu(lib):
     assert L.af_groupnorm_ws_floats(8) == 8 * 128 * 32 * 2        # [B][<=128 partial blocks][32 groups][sum, sumsq]
 
 
+def test_halo_scope_reads_no_operand_pointer_and_a_tail_without_a3_is_refused(lib):
+    """af_gemm_halo_variant answers for a host-side descriptor (no operands) what a launch would get; the K tail's operand checks are af_gemm's:
+    c3 > 0 with a null a3 is a bad argument on every tile, before any launch."""
+    L = lib.lib()
+    d = lib.GemmDesc()
+    d.taps, d.B, d.H, d.W, d.Ho, d.Wo, d.M, d.N, d.stride = 9, 2, 64, 64, 64, 64, 2 * 64 * 64, 320, 1
+    d.c1, d.c3, d.c4, d.K, d.kpad = 320, 256, 64, 9 * 320 + 320, 9 * 320 + 320
+    assert L.af_gemm_halo_variant(ctypes.byref(d)) == 1
+    d.a3 = d.a4 = 4096
+    assert L.af_gemm_halo_variant(ctypes.byref(d)) == 1
+    d.a1 = d.wt = d.out = 4096                               # (never dereferenced: the call is refused)
+    for tile in (14, 11, 1):
+        for a3, a4 in ((None, 4096), (4096, None)):
+            d.tile, d.a3, d.a4 = tile, a3, a4
+            assert L.af_gemm(ctypes.byref(d), None) == lib.AF_E_BADARG
+            assert b"the K tail needs taps == 9 and a3 (a4 when c4 > 0)" in L.af_last_error()
+
+
 def test_gemm_desc_matches_c_struct(lib, tmp_path):
     """sizeof/offsetof of af_gemm_desc as compiled by gcc == the ctypes mirror."""
     fields = [f[0] for f in lib.GemmDesc._fields_]
