@@ -35,7 +35,7 @@ EXPORTS = (
     "af_splitk_reduce", "af_groupnorm_splitk_ok", "af_groupnorm_splitk", "af_xattn_chain",
     "af_image_u8_to_nhwc_f16", "af_vae_latents_q_sample", "af_cfg_dpmpp_step", "af_cfg_lcm_step",
     "af_cfg_ddim_inpaint_step", "af_cfg_dpmpp_inpaint_step", "af_cfg_lcm_inpaint_step", "af_vae_latents_z_q_sample",
-    "af_vae_attention",
+    "af_vae_attention", "af_latent_resize_q_sample",
 )
 
 
@@ -148,6 +148,7 @@ def lib() -> C.CDLL:
     L.af_image_u8_to_nhwc_f16.argtypes = [vp, vp, i32, i32, i32, vp]
     L.af_vae_latents_q_sample.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, vp, i32, i32, i32, i32, vp]
     L.af_vae_latents_z_q_sample.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, i32, i32, i32, i32, vp]
+    L.af_latent_resize_q_sample.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp]
     blend = [vp, vp, vp, i32, i32, i64, f32, f32]
     L.af_cfg_ddim_inpaint_step.argtypes = L.af_cfg_ddim_step.argtypes[:-1] + blend + [vp]
     L.af_cfg_dpmpp_inpaint_step.argtypes = L.af_cfg_dpmpp_step.argtypes[:-1] + blend + [vp]

@@ -47,6 +47,12 @@ constant, the (cond, uncond) batch runs only when the scale is above 1, and ``fo
 step but the last.  Nothing is downloaded: ``lcm_lora_path`` is a local file or an in-memory state dict.  ``fuse_lcm_lora`` /
 ``unfuse_lcm_lora`` change the weights only; the sampler follows ``use_lcm``.
 
+``forward(..., hires_size=(W, H))`` (``text2img`` only; INTEGRATION.md "High-resolution text2img") samples in two passes, under any
+of the three samplers: the usual run at the size of ``noise``, then ``LatentDiffusion.hires_latents`` (one fused kernel: the latents
+resampled to the target size, ``hires_upscaler`` "bilinear" or "bicubic", and noised to the second pass's first timestep) and
+``sample_img2img`` over ``hires_strength`` of ``hires_steps`` (default ``num_inference_steps``) at the target size.  Antialiased,
+nearest, pixel-space and model-based upscalers, hires for img2img / inpaint and graph capture of the two passes are not built.
+
 SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, U-Net ensembles and the
 ConsistentID encoder are out of scope (external packages).  Of inpainting, 9-channel inpainting U-Nets, ``padding_mask_crop`` /
 pixel paste-back, caller-supplied ``masked_image_latents``, graph capture of the loop and automatic face masks are not built."""
@@ -57,7 +63,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import SD15_UNET_CONFIG
+from .. import SD15_UNET_CONFIG, ops
 from ..ldm.models.diffusion.ddim import DDIMSampler
 from ..ldm.models.diffusion.ddpm import LatentDiffusion
 from ..ldm.models.diffusion.dpm_solver import DPMSolverSampler
@@ -422,9 +428,12 @@ class AdaFaceWrapper(nn.Module):
     def forward(self, noise, prompt, prompt_embeds=None, negative_prompt=None, placeholder_tokens_pos="append", guidance_scale=6.0,
                 out_image_count=4, ref_img_strength=0.8, generator=None, ablate_prompt_only_placeholders=False,
                 ablate_prompt_no_placeholders=False, ablate_prompt_embed_type="ada", nonmix_prompt_emb_weight=0,
-                repeat_prompt_for_each_encoder=True, verbose=False, mask_image=None):
+                repeat_prompt_for_each_encoder=True, verbose=False, mask_image=None, hires_size=None, hires_strength=0.7,
+                hires_steps=None, hires_upscaler="bilinear"):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
+        if hires_size is not None:
+            hires_hw, hires_steps = self._check_hires(hires_size, hires_strength, hires_steps, hires_upscaler)
         inpaint = self.pipeline_name == "inpaint"
         if inpaint and mask_image is None:
             raise ValueError("the inpaint pipeline needs mask_image (white = repaint)")
@@ -479,9 +488,33 @@ class AdaFaceWrapper(nn.Module):
         noise = noise.to(device=self.device, dtype=torch.float32)
         latents, _ = sampler.sample(self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise,
                                     verbose=False, guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
+        if hires_size is not None:
+            _, t_first = sampler.img2img_steps(hires_steps, hires_strength)
+            x_t = self.ldm.hires_latents(latents, hires_hw, t_first, generator, hires_upscaler)
+            latents, _ = sampler.sample_img2img(hires_steps, hires_strength, out_image_count, x_t, cond, guidance_scale=guidance_scale,
+                                                unconditional_conditioning=uncond, generator=generator)
         if self.vae is None:
             return latents
         return self._to_pil(latents)
+
+    def _check_hires(self, hires_size, hires_strength, hires_steps, hires_upscaler):
+        """The refusals of high-resolution text2img (INTEGRATION.md "High-resolution text2img"), all before any GPU work.  Returns
+        the second pass's latent (H, W) and its step count."""
+        if self.pipeline_name != "text2img":
+            raise ValueError(f"hires_size is given but the pipeline is {self.pipeline_name!r}: only pipeline_name='text2img' runs two passes")
+        try:
+            W, H = (int(s) for s in hires_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"hires_size must be (W, H) in pixels, got {hires_size!r}") from None
+        if W % 64 or H % 64 or not (64 <= W <= MAX_IMAGE_SIDE and 64 <= H <= MAX_IMAGE_SIDE):
+            raise ValueError(f"hires_size sides must be multiples of 64 from 64 to {MAX_IMAGE_SIDE} pixels, got {W} x {H}")
+        if hires_upscaler not in ops.RESIZE_MODES:
+            raise ValueError(f"hires_upscaler must be one of {sorted(ops.RESIZE_MODES)}, got {hires_upscaler!r}")
+        steps = self.num_inference_steps if hires_steps is None else hires_steps
+        if not isinstance(steps, int) or not 1 <= steps <= self.ldm.num_timesteps:
+            raise ValueError(f"hires_steps must be an integer from 1 to {self.ldm.num_timesteps}, got {hires_steps!r}")
+        self._sampler().img2img_steps(steps, hires_strength)        # a bad strength, or more steps than the sampler takes
+        return (H // 8, W // 8), steps
 
     def _sampler(self):
         return LCMSampler(self.ldm) if self.use_lcm else SCHEDULERS[self.default_scheduler_name](self.ldm)

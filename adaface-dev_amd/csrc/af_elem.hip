@@ -1,5 +1,6 @@
 // af_elem.hip -- small element-wise kernels around the U-Net: timestep embedding, layout
-// conversion at the NCHW fp32 API boundary, classifier-free guidance + DDIM / DPM-Solver++ / LCM update, q_sample.
+// conversion at the NCHW fp32 API boundary, classifier-free guidance + DDIM / DPM-Solver++ / LCM update, q_sample, latent resize.
+#include <algorithm>
 #include <initializer_list>
 #include <type_traits>
 
@@ -627,6 +628,121 @@ extern "C" int af_vae_latents_z_q_sample(const void* h, const void* qw, const vo
                                          float sa, float sb, void* x_t, void* z, int B_img, int B_out, int hh, int ww, void* stream) {
   AF_REQUIRE(z, "af_vae_latents_z_q_sample: z is NULL");
   return vae_latents("af_vae_latents_z_q_sample", h, qw, qb, n_post, n_fwd, scale, sa, sb, x_t, z, B_img, B_out, hh, ww, stream);
+}
+
+namespace {
+
+// high-resolution text2img, between the passes (INTEGRATION.md "High-resolution text2img"): resample the first pass's latents and
+// noise them to the second pass's first timestep.  R is torch's F.interpolate(align_corners=False, antialias=False) as ATen's CPU
+// kernels compute it in fp32: the source coordinate of area_pixel_compute_source_index, and per output the taps of one axis
+// (2 bilinear, 4 bicubic with A = -0.75) summed left to right along the row first, then across the rows.  Every product and sum
+// is rounded on its own (contraction off), so the result does not depend on the form that stores it.
+enum : int { RESIZE_BILINEAR = 0, RESIZE_BICUBIC = 1 };
+
+// the taps of output `dst` on an axis of `in` source elements: indices (all inside [0, in - 1]) and weights
+template <int MODE>
+__device__ __forceinline__ void resize_taps(float scale, int dst, int in, int* idx, float* wt) {
+#pragma clang fp contract(off)
+  const float src = scale * ((float)dst + 0.5f) - 0.5f;
+  if (MODE == RESIZE_BILINEAR) {
+    const float s = fmaxf(src, 0.f);
+    const int i0 = min((int)s, in - 1);
+    const float l = s - (float)i0;
+    idx[0] = i0;
+    idx[1] = min(i0 + 1, in - 1);
+    wt[0] = 1.0f - l;
+    wt[1] = l;
+  } else {
+    const float fl = floorf(src);
+    const float t = src - fl;
+    const int i = (int)fl;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) idx[k] = min(max(i - 1 + k, 0), in - 1);
+    // ATen's get_cubic_upsample_coefficients: cubic_convolution2 at t + 1 and (1 - t) + 1, cubic_convolution1 at t and 1 - t
+    const float A = -0.75f, u = 1.0f - t, x0 = t + 1.0f, x3 = u + 1.0f;
+    wt[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
+    wt[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
+    wt[2] = ((A + 2.0f) * u - (A + 3.0f)) * u * u + 1.0f;
+    wt[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
+  }
+}
+
+// One thread per four adjacent outputs of a row (Y, X0 .. X0 + 3): its row taps and the column taps of its four outputs are
+// computed once and kept in registers while it walks planes blockIdx.y, blockIdx.y + gridDim.y, ...  The source plane is read
+// through the cache (neighbouring threads share most taps).  V4: W % 4 == 0 and out / noise 16-byte aligned, one 16-byte load
+// of noise and one 16-byte store; else one element at a time, X < W checked.  noise == NULL stores R(x) itself.
+template <int MODE, bool V4>
+__global__ __launch_bounds__(256) void latent_resize_q_sample_kernel(const float* __restrict__ x, const float* __restrict__ noise,
+                                                                     float* __restrict__ out, int P, int h, int w, int H, int W,
+                                                                     float scale_y, float scale_x, float sa, float sb) {
+#pragma clang fp contract(off)
+  constexpr int T = MODE == RESIZE_BICUBIC ? 4 : 2;
+  const int groups = (W + 3) >> 2;
+  const int item = blockIdx.x * 256 + threadIdx.x;
+  if (item >= H * groups) return;
+  const int Y = item / groups, X0 = (item - Y * groups) * 4;
+  int yi[T], xi[4][T];
+  float yw[T], xw[4][T];
+  resize_taps<MODE>(scale_y, Y, h, yi, yw);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) resize_taps<MODE>(scale_x, X0 + j, w, xi[j], xw[j]);
+  for (int p = blockIdx.y; p < P; p += gridDim.y) {
+    const float* xp = x + (long)p * h * w;
+    float r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float acc = 0.f;
+#pragma unroll
+      for (int a = 0; a < T; ++a) {
+        const float* row = xp + yi[a] * w;
+        float s = row[xi[j][0]] * xw[j][0];
+#pragma unroll
+        for (int b = 1; b < T; ++b) s = s + row[xi[j][b]] * xw[j][b];
+        acc = a == 0 ? s * yw[0] : acc + s * yw[a];
+      }
+      r[j] = acc;
+    }
+    const long o = ((long)p * H + Y) * W + X0;
+    if (V4) {
+      float4 y = make_float4(r[0], r[1], r[2], r[3]);
+      if (noise) {
+        const float4 n = *reinterpret_cast<const float4*>(noise + o);
+        y = make_float4(fmaf(sb, n.x, sa * r[0]), fmaf(sb, n.y, sa * r[1]), fmaf(sb, n.z, sa * r[2]), fmaf(sb, n.w, sa * r[3]));
+      }
+      *reinterpret_cast<float4*>(out + o) = y;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (X0 + j < W) out[o + j] = noise ? fmaf(sb, noise[o + j], sa * r[j]) : r[j];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int af_latent_resize_q_sample(const void* x, const void* noise, void* out, int P, int h, int w, int H, int W, int mode,
+                                         float sa, float sb, void* stream) {
+  AF_REQUIRE(x && out, "af_latent_resize_q_sample: x or out is NULL");
+  AF_REQUIRE(P > 0 && h > 0 && w > 0 && H > 0 && W > 0, "af_latent_resize_q_sample: every dimension must be at least 1");
+  AF_REQUIRE(mode == RESIZE_BILINEAR || mode == RESIZE_BICUBIC, "af_latent_resize_q_sample: mode must be 0 (bilinear) or 1 (bicubic)");
+  AF_REQUIRE((long)P * H * W < (1L << 31) && (long)P * h * w < (1L << 31),
+             "af_latent_resize_q_sample: needs fewer than 2^31 input and output elements");
+  const bool v4 = W % 4 == 0 && ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(noise)) & 15) == 0;
+  // enough blocks to fill the GPU come first; past that a thread walks planes with its taps in registers
+  const long gx = ((long)H * ((W + 3) / 4) + 255) / 256;
+  const long gy = std::min<long>(std::min<long>(P, 65535), std::max<long>(1, (1024 + gx - 1) / gx));
+  const dim3 grid((unsigned)gx, (unsigned)gy);
+  const float scale_y = (float)h / (float)H, scale_x = (float)w / (float)W;
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)noise, (float*)out, P, h, w, H,
+                       W, scale_y, scale_x, sa, sb);
+  };
+  if (mode == RESIZE_BILINEAR && v4) launch(latent_resize_q_sample_kernel<RESIZE_BILINEAR, true>);
+  else if (mode == RESIZE_BILINEAR) launch(latent_resize_q_sample_kernel<RESIZE_BILINEAR, false>);
+  else if (v4) launch(latent_resize_q_sample_kernel<RESIZE_BICUBIC, true>);
+  else launch(latent_resize_q_sample_kernel<RESIZE_BICUBIC, false>);
+  return af_check_launch("af_latent_resize_q_sample");
 }
 
 // dS = P * (dP - rowsum(P * dP)): the softmax backward of the VAE decoder's single-head attention (rows like af_softmax_rows)

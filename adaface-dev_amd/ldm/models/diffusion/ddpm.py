@@ -10,6 +10,7 @@ The loss assemblies of the compositional-distillation and normal-recon iteration
 ``device``, ``q_sample``, ``apply_model``, ``model.diffusion_model``) keep working.
 """
 import copy
+import math
 import os
 from functools import partial
 
@@ -418,6 +419,20 @@ class LatentDiffusion(CompReconLossesMixin, nn.Module):
         n_fwd = n_fwd.contiguous()
         out = vae.encode_q_sample(images_u8.to(dev).contiguous(), n_post.contiguous(), n_fwd, self.scale_factor, sa, sb, with_z=with_z)
         return (*out, n_fwd) if with_z else (out,)
+
+    @torch.no_grad()
+    def hires_latents(self, latents, size_hw, t_first, generator=None, mode="bilinear"):
+        """Between the passes of high-resolution text2img (INTEGRATION.md "High-resolution text2img"): the first pass's latents
+        fp32 [B, 4, h, w] resampled to size_hw = (H, W) as F.interpolate(mode, align_corners=False) and noised to timestep t_first,
+        x_t = sa r + sb n_hr with (sa, sb) = (sqrt(abar), sqrt(1 - abar)) in fp64.  n_hr [B, 4, H, W] is one torch.randn on the
+        generator's device (the default CUDA generator when None), moved to the model's device.  One launch."""
+        dev = self.device
+        H, W = (int(s) for s in size_hw)
+        latents = latents.to(device=dev, dtype=torch.float32).contiguous()
+        gdev = generator.device if generator is not None else dev
+        n_hr = torch.randn((latents.shape[0], latents.shape[1], H, W), generator=generator, device=gdev).to(dev).contiguous()
+        ac = float(self.alphas_cumprod[int(t_first)].double())
+        return ops.latent_resize_q_sample(latents, (H, W), mode, n_hr, math.sqrt(ac), math.sqrt(1.0 - ac))
 
     def q_sample(self, x_start, t, noise=None):
         noise = torch.randn_like(x_start) if noise is None else noise

@@ -1060,6 +1060,34 @@ def vae_latents_q_sample(h: torch.Tensor, qw: torch.Tensor, qb: torch.Tensor, n_
     return x_t, z
 
 
+RESIZE_MODES = {"bilinear": 0, "bicubic": 1}
+
+
+def latent_resize_q_sample(x: torch.Tensor, size_hw, mode: str = "bilinear", noise: Optional[torch.Tensor] = None, sa: float = 1.0,
+                           sb: float = 0.0) -> torch.Tensor:
+    """x fp32 [B, C, h, w] -> fp32 [B, C, H, W], size_hw = (H, W): F.interpolate(x, size_hw, mode, align_corners=False) in fp32
+    ("bilinear" or "bicubic", not antialiased), then sa r + sb noise with ``noise`` fp32 [B, C, H, W]; the resampled tensor itself
+    when ``noise`` is None (sa, sb unused).  One launch (af_latent_resize_q_sample)."""
+    if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous() or x.dim() != 4:
+        raise RuntimeError(f"latent_resize_q_sample.x: expected a contiguous fp32 device tensor [B, C, h, w], got {x.dtype} "
+                           f"{tuple(x.shape)} on {x.device}")
+    if mode not in RESIZE_MODES:
+        raise RuntimeError(f"latent_resize_q_sample: mode must be one of {sorted(RESIZE_MODES)}, got {mode!r}")
+    B, Cn, h, w = x.shape
+    H, W = (int(s) for s in size_hw)
+    if H < 1 or W < 1:
+        raise RuntimeError(f"latent_resize_q_sample: size_hw must be positive, got {(H, W)}")
+    if noise is not None and (noise.dtype != torch.float32 or noise.device != x.device or not noise.is_contiguous()
+                              or tuple(noise.shape) != (B, Cn, H, W)):
+        raise RuntimeError(f"latent_resize_q_sample.noise: expected contiguous fp32 {(B, Cn, H, W)} on {x.device}, got {noise.dtype} "
+                           f"{tuple(noise.shape)} on {noise.device}")
+    out = torch.empty((B, Cn, H, W), dtype=torch.float32, device=x.device)
+    rc = _lib.lib().af_latent_resize_q_sample(_p(x), _p(noise), _p(out), B * Cn, h, w, H, W, RESIZE_MODES[mode], float(sa), float(sb),
+                                              _stream())
+    _lib.check(rc, "af_latent_resize_q_sample")
+    return out
+
+
 # ----------------------------------------------------------------------------- backward ops
 def groupnorm_bwd(x, gamma, beta, stats, dy, silu, *, x2=None, add=None, groups=32):
     """Input gradient of groupnorm(+SiLU): returns dx (or (dx1, dx2) when x2 is given)."""

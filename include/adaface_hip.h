@@ -420,6 +420,12 @@ int af_vae_latents_q_sample(const void* h, const void* qw, const void* qb, const
 /* the same, also writing the image latents z fp32 NCHW [B_img,4,hh,ww] (inpainting blends with them).  z must not be NULL.     */
 int af_vae_latents_z_q_sample(const void* h, const void* qw, const void* qb, const void* n_post, const void* n_fwd, float scale,
                               float sa, float sb, void* x_t, void* z, int B_img, int B_out, int hh, int ww, void* stream);
+/* high-resolution text2img, between the two passes, one launch:
+ * out[p, Y, X] = fma(sb, noise[p, Y, X], sa * R(x)[p, Y, X]) over P = B*C planes; x fp32 [P, h, w], out / noise fp32 [P, H, W];
+ * R = torch's F.interpolate(align_corners=False, antialias=False): mode 0 bilinear, 1 bicubic (A = -0.75);
+ * noise == NULL: out = R(x) exactly (sa, sb ignored).  No workspace. */
+int af_latent_resize_q_sample(const void* x, const void* noise, void* out, int P, int h, int w, int H, int W, int mode,
+                              float sa, float sb, void* stream);
 
 /* y = x * sigmoid(x), fp16 (nn.SiLU on the time embedding, openaimodel.py:219-220) */
 int af_silu_f16(const void* x, void* y, int64_t n, void* stream);
