@@ -1,8 +1,6 @@
 // af_elem.hip -- small element-wise kernels around the U-Net: timestep embedding, layout
 // conversion at the NCHW fp32 API boundary, classifier-free guidance + DDIM / DPM-Solver++ / LCM update, q_sample, latent resize.
 #include <algorithm>
-#include <initializer_list>
-#include <type_traits>
 
 #include "af_common.h"
 
@@ -158,141 +156,92 @@ __device__ __forceinline__ float4 blend_v4(float4 y, long i, const InpaintBlend&
                      blend_elem<BLEND>(y.z, m.z, z.z, nz.z, bl), blend_elem<BLEND>(y.w, m.w, z.w, nz.w, bl));
 }
 
-// classifier-free guidance + one DDIM step (ddim.py:253-255, 279-301, sigma = 0), per element:
-// e = e_u + g (e_c - e_u); pred_x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t); x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev) e.
-// pred_x0 may be NULL.  V4: 16-byte accesses, n % 4 == 0, all pointers aligned (the plain step runs the scalar form only).
-struct DdimCoefs {
-  float g, sqrt_one_minus_at, sqrt_at, sqrt_aprev, dir_coef;
-};
-
-// The roundings are spelled out (two fmas, two products and their sum) so that every form computes what the plain step always has.
-__device__ __forceinline__ float ddim_elem(float ec, float eu, int has_uncond, float x, const DdimCoefs& k, float& p0) {
+// The fused sampler steps: classifier-free guidance + one DDIM / DPM-Solver++ / LCM update + the inpaint blend, per element.
+// cfg_step_kernel<Step, V4, BLEND> is their one frame: the bounds check, the loads of e_c, e_u, x and the step's extra inputs,
+// e = e_u + g (e_c - e_u) (e_c alone when eps2 has no unconditional half), Step::elem, the store of the auxiliary x0-like output
+// (skipped when NULL, which only DDIM allows), the blend, the store of the new latent.  V4: one thread per float4, 16-byte accesses;
+// run_cfg_step picks it when n % 4 == 0 and every pointer the form touches is aligned.
+// A Step carries its coefficients, says how many of the two extra input streams it reads (NIN; a stream at or past NIN is never
+// dereferenced and may be NULL) and has one element function, elem(e, x, in0, in1, aux) -> new latent, aux = the x0-like output.
+// guided() and every elem spell out their roundings (fmaf, contraction off), so the scalar, 16-byte and blend forms agree bit for bit.
+// The step types keep the samplers' names in the kernel names: tools/profile_*.sh find the step boundary by "cfg_ddim".
+__device__ __forceinline__ float guided(float ec, float eu, int has_uncond, float g) {
 #pragma clang fp contract(off)
-  const float e = has_uncond ? fmaf(k.g, ec - eu, eu) : ec;
-  p0 = fmaf(-k.sqrt_one_minus_at, e, x) / k.sqrt_at;
-  return k.sqrt_aprev * p0 + k.dir_coef * e;
+  return has_uncond ? fmaf(g, ec - eu, eu) : ec;
 }
 
-template <int BLEND, bool V4>
-__global__ void cfg_ddim_kernel(const float* __restrict__ eps2, const float* __restrict__ x, float* __restrict__ x_prev,
-                                float* __restrict__ pred_x0, long n, int has_uncond, DdimCoefs k, InpaintBlend bl) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (V4) {
-    if (i >= n / 4) return;
-    const float4 ec = reinterpret_cast<const float4*>(eps2)[i];
-    const float4 eu = has_uncond ? reinterpret_cast<const float4*>(eps2 + n)[i] : ec;
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    float4 y, p0;
-    y.x = ddim_elem(ec.x, eu.x, has_uncond, xv.x, k, p0.x);
-    y.y = ddim_elem(ec.y, eu.y, has_uncond, xv.y, k, p0.y);
-    y.z = ddim_elem(ec.z, eu.z, has_uncond, xv.z, k, p0.z);
-    y.w = ddim_elem(ec.w, eu.w, has_uncond, xv.w, k, p0.w);
-    if (pred_x0) reinterpret_cast<float4*>(pred_x0)[i] = p0;
-    reinterpret_cast<float4*>(x_prev)[i] = blend_v4<BLEND>(y, i, bl);
-  } else {
-    if (i >= n) return;
-    const float ec = eps2[i];
-    const float eu = has_uncond ? eps2[n + i] : ec;
-    float p0;
-    const float y = ddim_elem(ec, eu, has_uncond, x[i], k, p0);
-    if (pred_x0) pred_x0[i] = p0;
-    x_prev[i] = blend_scalar<BLEND>(y, i, bl);
+// DDIM (ddim.py:253-255, 279-301, sigma = 0): pred_x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t); x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev) e.
+struct cfg_ddim {
+  static constexpr int NIN = 0;
+  float sqrt_one_minus_at, sqrt_at, sqrt_aprev, dir_coef;
+  // The roundings are spelled out (with guided(): two fmas, two products and their sum) so that every form computes what the plain
+  // step always has.
+  __device__ __forceinline__ float elem(float e, float x, float, float, float& p0) const {
+#pragma clang fp contract(off)
+    p0 = fmaf(-sqrt_one_minus_at, e, x) / sqrt_at;
+    return sqrt_aprev * p0 + dir_coef * e;
   }
-}
-
-// classifier-free guidance + one DPM-Solver++ (2S, midpoint) step in data-prediction form, per element:
-// e = e_u + g (e_c - e_u); x0 = (x - sigma_s e) / alpha_s; x_out = c_base x_base + c0 x0 + c1 x0_prev.
-// HAS_PREV = false never touches x0_prev (the order-1 steps, c1 == 0).  V4: 16-byte accesses, n % 4 == 0, all pointers aligned.
-// The *_elem helpers spell out their roundings (fmaf, contraction off), so the scalar, 16-byte and blend forms agree bit for bit.
-struct DpmppCoefs {
-  float g, sigma_s, alpha_s, c_base, c0, c1;
 };
 
+// DPM-Solver++ (2S, midpoint) in data-prediction form: x0 = (x - sigma_s e) / alpha_s; x_out = c_base x_base + c0 x0 + c1 x0_prev.
+// Inputs: x_base, x0_prev.  HAS_PREV = false never touches x0_prev (the order-1 steps, c1 == 0).
 template <bool HAS_PREV>
-__device__ __forceinline__ float dpmpp_elem(float ec, float eu, int has_uncond, float x, float xb, float xp, const DpmppCoefs& k,
-                                            float& x0) {
+struct cfg_dpmpp {
+  static constexpr int NIN = HAS_PREV ? 2 : 1;
+  float sigma_s, alpha_s, c_base, c0, c1;
+  __device__ __forceinline__ float elem(float e, float x, float xb, float xp, float& x0) const {
 #pragma clang fp contract(off)
-  const float e = has_uncond ? fmaf(k.g, ec - eu, eu) : ec;
-  x0 = fmaf(-k.sigma_s, e, x) / k.alpha_s;
-  const float y = fmaf(k.c0, x0, k.c_base * xb);
-  return HAS_PREV ? fmaf(k.c1, xp, y) : y;
-}
-
-template <bool HAS_PREV, bool V4, int BLEND = BLEND_NONE>
-__global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const float* __restrict__ eps2, const float* __restrict__ x,
-                                                        const float* __restrict__ x_base, const float* __restrict__ x0_prev,
-                                                        float* __restrict__ x_out, float* __restrict__ x0_out, long n, int has_uncond,
-                                                        DpmppCoefs k, InpaintBlend bl) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (V4) {
-    if (i >= n / 4) return;
-    const float4 ec = reinterpret_cast<const float4*>(eps2)[i];
-    const float4 eu = has_uncond ? reinterpret_cast<const float4*>(eps2 + n)[i] : ec;
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    const float4 xb = reinterpret_cast<const float4*>(x_base)[i];
-    const float4 xp = HAS_PREV ? reinterpret_cast<const float4*>(x0_prev)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 y, p0;
-    y.x = dpmpp_elem<HAS_PREV>(ec.x, eu.x, has_uncond, xv.x, xb.x, xp.x, k, p0.x);
-    y.y = dpmpp_elem<HAS_PREV>(ec.y, eu.y, has_uncond, xv.y, xb.y, xp.y, k, p0.y);
-    y.z = dpmpp_elem<HAS_PREV>(ec.z, eu.z, has_uncond, xv.z, xb.z, xp.z, k, p0.z);
-    y.w = dpmpp_elem<HAS_PREV>(ec.w, eu.w, has_uncond, xv.w, xb.w, xp.w, k, p0.w);
-    reinterpret_cast<float4*>(x0_out)[i] = p0;
-    reinterpret_cast<float4*>(x_out)[i] = blend_v4<BLEND>(y, i, bl);
-  } else {
-    if (i >= n) return;
-    const float ec = eps2[i];
-    const float eu = has_uncond ? eps2[n + i] : ec;
-    float p0;
-    const float y = dpmpp_elem<HAS_PREV>(ec, eu, has_uncond, x[i], x_base[i], HAS_PREV ? x0_prev[i] : 0.f, k, p0);
-    x0_out[i] = p0;
-    x_out[i] = blend_scalar<BLEND>(y, i, bl);
+    x0 = fmaf(-sigma_s, e, x) / alpha_s;
+    const float y = fmaf(c0, x0, c_base * xb);
+    return HAS_PREV ? fmaf(c1, xp, y) : y;
   }
-}
-
-// classifier-free guidance + one LCM (multistep consistency) step, per element:
-// e = e_u + g (e_c - e_u); x0 = (x - sqrt(1 - abar_t) e) / sqrt(abar_t); d = c_out x0 + c_skip x;
-// x_next = sqrt(abar_next) d + sqrt(1 - abar_next) noise, or d on the last step (HAS_NOISE = false never touches noise).
-// V4: 16-byte accesses, n % 4 == 0, all pointers aligned.
-struct LcmCoefs {
-  float g, sa, sb, c_out, c_skip, sa_next, sb_next;
 };
 
+// LCM (multistep consistency): x0 = (x - sqrt(1 - abar_t) e) / sqrt(abar_t); d = c_out x0 + c_skip x;
+// x_next = sqrt(abar_next) d + sqrt(1 - abar_next) noise, or d on the last step.  Input: noise; HAS_NOISE = false never touches it.
 template <bool HAS_NOISE>
-__device__ __forceinline__ float lcm_elem(float ec, float eu, int has_uncond, float x, float nz, const LcmCoefs& k, float& d) {
+struct cfg_lcm {
+  static constexpr int NIN = HAS_NOISE ? 1 : 0;
+  float sa, sb, c_out, c_skip, sa_next, sb_next;
+  __device__ __forceinline__ float elem(float e, float x, float nz, float, float& d) const {
 #pragma clang fp contract(off)
-  const float e = has_uncond ? fmaf(k.g, ec - eu, eu) : ec;
-  const float x0 = fmaf(-k.sb, e, x) / k.sa;
-  d = fmaf(k.c_skip, x, k.c_out * x0);
-  return HAS_NOISE ? fmaf(k.sb_next, nz, k.sa_next * d) : d;
-}
+    const float x0 = fmaf(-sb, e, x) / sa;
+    d = fmaf(c_skip, x, c_out * x0);
+    return HAS_NOISE ? fmaf(sb_next, nz, sa_next * d) : d;
+  }
+};
 
-template <bool HAS_NOISE, bool V4, int BLEND = BLEND_NONE>
-__global__ __launch_bounds__(256) void cfg_lcm_kernel(const float* __restrict__ eps2, const float* __restrict__ x,
-                                                      const float* __restrict__ noise, float* __restrict__ x_next,
-                                                      float* __restrict__ denoised, long n, int has_uncond, LcmCoefs k,
-                                                      InpaintBlend bl) {
+template <class Step, bool V4, int BLEND>
+__global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__ eps2, const float* __restrict__ x,
+                                                       const float* __restrict__ in0, const float* __restrict__ in1,
+                                                       float* __restrict__ out, float* __restrict__ aux, long n, int has_uncond,
+                                                       float g, Step st, InpaintBlend bl) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (V4) {
     if (i >= n / 4) return;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 ec = reinterpret_cast<const float4*>(eps2)[i];
     const float4 eu = has_uncond ? reinterpret_cast<const float4*>(eps2 + n)[i] : ec;
     const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    const float4 nz = HAS_NOISE ? reinterpret_cast<const float4*>(noise)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 y, d;
-    y.x = lcm_elem<HAS_NOISE>(ec.x, eu.x, has_uncond, xv.x, nz.x, k, d.x);
-    y.y = lcm_elem<HAS_NOISE>(ec.y, eu.y, has_uncond, xv.y, nz.y, k, d.y);
-    y.z = lcm_elem<HAS_NOISE>(ec.z, eu.z, has_uncond, xv.z, nz.z, k, d.z);
-    y.w = lcm_elem<HAS_NOISE>(ec.w, eu.w, has_uncond, xv.w, nz.w, k, d.w);
-    reinterpret_cast<float4*>(denoised)[i] = d;
-    reinterpret_cast<float4*>(x_next)[i] = blend_v4<BLEND>(y, i, bl);
+    const float4 a = Step::NIN > 0 ? reinterpret_cast<const float4*>(in0)[i] : zero;
+    const float4 b = Step::NIN > 1 ? reinterpret_cast<const float4*>(in1)[i] : zero;
+    float4 y, x0;
+    y.x = st.elem(guided(ec.x, eu.x, has_uncond, g), xv.x, a.x, b.x, x0.x);
+    y.y = st.elem(guided(ec.y, eu.y, has_uncond, g), xv.y, a.y, b.y, x0.y);
+    y.z = st.elem(guided(ec.z, eu.z, has_uncond, g), xv.z, a.z, b.z, x0.z);
+    y.w = st.elem(guided(ec.w, eu.w, has_uncond, g), xv.w, a.w, b.w, x0.w);
+    if (aux) reinterpret_cast<float4*>(aux)[i] = x0;
+    reinterpret_cast<float4*>(out)[i] = blend_v4<BLEND>(y, i, bl);
   } else {
     if (i >= n) return;
     const float ec = eps2[i];
     const float eu = has_uncond ? eps2[n + i] : ec;
-    float d;
-    const float y = lcm_elem<HAS_NOISE>(ec, eu, has_uncond, x[i], HAS_NOISE ? noise[i] : 0.f, k, d);
-    denoised[i] = d;
-    x_next[i] = blend_scalar<BLEND>(y, i, bl);
+    const float a = Step::NIN > 0 ? in0[i] : 0.f;
+    const float b = Step::NIN > 1 ? in1[i] : 0.f;
+    float x0;
+    const float y = st.elem(guided(ec, eu, has_uncond, g), x[i], a, b, x0);
+    if (aux) aux[i] = x0;
+    out[i] = blend_scalar<BLEND>(y, i, bl);
   }
 }
 
@@ -366,25 +315,6 @@ __global__ void silu_kernel(const half_t* __restrict__ x, half_t* __restrict__ y
 
 inline dim3 grid1d(long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
-// The launch of a fused sampler step KERNEL<FLAG, V4> over n fp32 elements: V4 (one thread per float4) when n % 4 == 0, `vec_ok`
-// holds and every pointer in `ptrs` is 16-byte aligned (NULL for one the FLAG = false form never touches), else one thread per
-// element.  `launch(flag, v4, grid)` gets FLAG and V4 as std::bool_constant, to instantiate the kernel with.
-template <typename Launch>
-void launch_flag_v4(bool flag, long n, std::initializer_list<const void*> ptrs, Launch launch, bool vec_ok = true) {
-  uintptr_t align = 0;
-  for (const void* p : ptrs) align |= reinterpret_cast<uintptr_t>(p);
-  const bool v4 = vec_ok && n % 4 == 0 && (align & 15) == 0;
-  const dim3 grid = grid1d(v4 ? n / 4 : n);
-  if (flag && v4)
-    launch(std::true_type{}, std::true_type{}, grid);
-  else if (flag)
-    launch(std::true_type{}, std::false_type{}, grid);
-  else if (v4)
-    launch(std::false_type{}, std::true_type{}, grid);
-  else
-    launch(std::false_type{}, std::false_type{}, grid);
-}
-
 }  // namespace
 
 extern "C" int af_timestep_embedding(const void* timesteps_i64, void* out, int B, int dim, float max_period, void* stream) {
@@ -413,149 +343,151 @@ extern "C" int af_nhwc_f16_to_nchw_f32(const void* x, void* y, int B, int C, int
 
 namespace {
 
+// a fused sampler step's streams as its entry point gets them: in[] are the step's extra inputs (cfg_step_kernel); out is the new
+// latent, aux the x0-like output
+struct StepIO {
+  const void* eps2;
+  const void* x;
+  const void* in[2];
+  void* out;
+  void* aux;
+  int64_t n;
+  int has_uncond;
+  float guidance;
+};
+
+// an inpaint entry point's blend arguments
+struct BlendArgs {
+  const void* z;
+  const void* noise;
+  const void* mask;
+  int B_img, B_mask;
+  int64_t hw;
+  float sa_next, sb_next;
+};
+
 // argument checks and the descriptor of an inpaint step's blend; AF_OK or the af_fail code
-int make_blend(const char* who, int64_t n, const void* z, const void* noise, const void* mask, int B_img, int B_mask, int64_t hw,
-               float sa_next, float sb_next, InpaintBlend& bl) {
-  const std::string w(who);
-  AF_REQUIRE(z && mask && B_img > 0 && B_mask > 0 && hw > 0 && n % (4 * hw) == 0, w + ": bad blend argument");
-  AF_REQUIRE(n < (int64_t(1) << 31) && (int64_t)B_img * 4 * hw < (int64_t(1) << 31), w + ": blend needs fewer than 2^31 elements");
-  AF_REQUIRE(!noise || (std::isfinite(sa_next) && std::isfinite(sb_next)), w + ": blend coefficients must be finite");
-  bl = InpaintBlend{(const float*)z, (const float*)noise, (const float*)mask, sa_next, sb_next, B_img, B_mask, (long)hw};
+int make_blend(const std::string& w, int64_t n, const BlendArgs& a, InpaintBlend& bl) {
+  AF_REQUIRE(a.z && a.mask && a.B_img > 0 && a.B_mask > 0 && a.hw > 0 && n % (4 * a.hw) == 0, w + ": bad blend argument");
+  AF_REQUIRE(n < (int64_t(1) << 31) && (int64_t)a.B_img * 4 * a.hw < (int64_t(1) << 31), w + ": blend needs fewer than 2^31 elements");
+  AF_REQUIRE(!a.noise || (std::isfinite(a.sa_next) && std::isfinite(a.sb_next)), w + ": blend coefficients must be finite");
+  bl = InpaintBlend{(const float*)a.z, (const float*)a.noise, (const float*)a.mask, a.sa_next, a.sb_next, a.B_img, a.B_mask, (long)a.hw};
   return AF_OK;
 }
 
-// the step's launch with the blend's form: BLEND_NOISED when it has noise, else BLEND_CLEAN; V4 also needs hw % 4 == 0 and the
-// blend's pointers aligned.  launch(flag, v4, blend, grid) gets all three as compile-time constants.
-template <typename Launch>
-void launch_blend(bool flag, long n, std::initializer_list<const void*> ptrs, const InpaintBlend& bl, Launch launch) {
-  uintptr_t align = reinterpret_cast<uintptr_t>(bl.z) | reinterpret_cast<uintptr_t>(bl.noise) | reinterpret_cast<uintptr_t>(bl.mask);
-  for (const void* p : ptrs) align |= reinterpret_cast<uintptr_t>(p);
-  const bool noised = bl.noise != nullptr;
-  launch_flag_v4(flag, n, {(const void*)align}, [&](auto f, auto v4, dim3 grid) {
-    if (noised)
-      launch(f, v4, std::integral_constant<int, BLEND_NOISED>{}, grid);
-    else
-      launch(f, v4, std::integral_constant<int, BLEND_CLEAN>{}, grid);
-  }, bl.hw % 4 == 0);
+// What the six step entry points share once their own checks have passed: the blend's checks (`blend` is NULL for a plain step),
+// the choice of cfg_step_kernel<Step, V4, BLEND>, its launch over io.n fp32 elements and the launch's status.
+// BLEND: none without a blend, else BLEND_NOISED when the blend has noise and BLEND_CLEAN when not.  V4 (one thread per float4) when
+// `vec_ok`, n % 4 == 0 and every pointer the form touches is 16-byte aligned (a NULL aux counts as aligned, an input the Step does
+// not read is not looked at); with a blend also hw % 4 == 0 (four elements share b and c) and the blend's pointers aligned.  Else
+// one thread per element.
+template <class Step>
+int run_cfg_step(const std::string& who, const Step& st, const StepIO& io, const BlendArgs* blend, void* stream, bool vec_ok = true) {
+  auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  uintptr_t align = bits(io.eps2) | bits(io.x) | bits(io.out) | bits(io.aux);
+  for (int j = 0; j < Step::NIN; ++j) align |= bits(io.in[j]);
+  InpaintBlend bl{};
+  int form = BLEND_NONE;
+  if (blend) {
+    if (int rc = make_blend(who, io.n, *blend, bl)) return rc;
+    form = bl.noise ? BLEND_NOISED : BLEND_CLEAN;
+    align |= bits(bl.z) | bits(bl.noise) | bits(bl.mask);
+    vec_ok = vec_ok && bl.hw % 4 == 0;
+  }
+  const bool v4 = vec_ok && io.n % 4 == 0 && (align & 15) == 0;
+  using Kernel = void (*)(const float*, const float*, const float*, const float*, float*, float*, long, int, float, Step, InpaintBlend);
+  static constexpr Kernel kernels[3][2] = {
+      {cfg_step_kernel<Step, false, BLEND_NONE>, cfg_step_kernel<Step, true, BLEND_NONE>},
+      {cfg_step_kernel<Step, false, BLEND_NOISED>, cfg_step_kernel<Step, true, BLEND_NOISED>},
+      {cfg_step_kernel<Step, false, BLEND_CLEAN>, cfg_step_kernel<Step, true, BLEND_CLEAN>},
+  };
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  hipLaunchKernelGGL(kernels[form][v4], grid1d(v4 ? io.n / 4 : io.n), dim3(256), 0, (hipStream_t)stream, (const float*)io.eps2,
+                     (const float*)io.x, (const float*)io.in[0], (const float*)io.in[1], (float*)io.out, (float*)io.aux, (long)io.n,
+                     io.has_uncond, io.guidance, st, bl);
+  return af_check_launch(who.c_str());
 }
 
-// fp32 scalar arithmetic exactly as ddim.py:279-301 (torch.full(..., fp32).sqrt())
-DdimCoefs ddim_coefs(float guidance, float a_t, float a_prev) {
-  return DdimCoefs{guidance, sqrtf(1.0f - a_t), sqrtf(a_t), sqrtf(a_prev), sqrtf(1.0f - a_prev)};
+// the count and the pointers every step needs, and its first `n_in` inputs; `aux_optional`: the step may skip its x0-like output
+int check_step_io(const std::string& w, const StepIO& io, int n_in, bool aux_optional) {
+  bool ok = io.eps2 && io.x && io.out && (io.aux || aux_optional) && io.n > 0;
+  for (int j = 0; j < n_in; ++j) ok = ok && io.in[j];
+  AF_REQUIRE(ok, w + ": bad argument");
+  return AF_OK;
+}
+
+int ddim_step(const std::string& w, const StepIO& io, float a_t, float a_prev, const BlendArgs* blend, void* stream, bool vec_ok) {
+  if (int rc = check_step_io(w, io, 0, true)) return rc;
+  AF_REQUIRE(a_t > 0.f && a_t <= 1.f && a_prev > 0.f && a_prev <= 1.f, w + ": alphas must be in (0, 1]");
+  // fp32 scalar arithmetic exactly as ddim.py:279-301 (torch.full(..., fp32).sqrt())
+  const cfg_ddim st{sqrtf(1.0f - a_t), sqrtf(a_t), sqrtf(a_prev), sqrtf(1.0f - a_prev)};
+  return run_cfg_step(w, st, io, blend, stream, vec_ok);
+}
+
+int dpmpp_step(const std::string& w, const StepIO& io, float alpha_s, float sigma_s, float c_base, float c0, float c1,
+               const BlendArgs* blend, void* stream) {
+  if (int rc = check_step_io(w, io, 1, false)) return rc;                     // x_base
+  AF_REQUIRE(alpha_s > 0.f && alpha_s <= 1.f && sigma_s >= 0.f && sigma_s < 1.f, w + ": need alpha_s in (0, 1] and sigma_s in [0, 1)");
+  AF_REQUIRE(std::isfinite(io.guidance) && std::isfinite(c_base) && std::isfinite(c0) && std::isfinite(c1),
+             w + ": coefficients must be finite");
+  AF_REQUIRE(io.in[1] || c1 == 0.f, w + ": x0_prev is NULL but c1 != 0");
+  if (c1 != 0.f) return run_cfg_step(w, cfg_dpmpp<true>{sigma_s, alpha_s, c_base, c0, c1}, io, blend, stream);
+  return run_cfg_step(w, cfg_dpmpp<false>{sigma_s, alpha_s, c_base, c0, c1}, io, blend, stream);
+}
+
+int lcm_step(const std::string& w, const StepIO& io, float sqrt_a, float sqrt_1ma, float c_out, float c_skip, float sqrt_a_next,
+             float sqrt_1ma_next, const BlendArgs* blend, void* stream) {
+  if (int rc = check_step_io(w, io, 0, false)) return rc;
+  AF_REQUIRE(sqrt_a > 0.f && sqrt_a <= 1.f && sqrt_1ma >= 0.f && sqrt_1ma < 1.f, w + ": need sqrt_a in (0, 1] and sqrt_1ma in [0, 1)");
+  AF_REQUIRE(std::isfinite(io.guidance) && std::isfinite(c_out) && std::isfinite(c_skip) && std::isfinite(sqrt_a_next) &&
+                 std::isfinite(sqrt_1ma_next),
+             w + ": coefficients must be finite");
+  const bool has_noise = io.in[0] != nullptr;
+  AF_REQUIRE(!has_noise || (sqrt_a_next > 0.f && sqrt_a_next <= 1.f && sqrt_1ma_next >= 0.f && sqrt_1ma_next < 1.f),
+             w + ": need sqrt_a_next in (0, 1] and sqrt_1ma_next in [0, 1)");
+  if (has_noise) return run_cfg_step(w, cfg_lcm<true>{sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next, sqrt_1ma_next}, io, blend, stream);
+  return run_cfg_step(w, cfg_lcm<false>{sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next, sqrt_1ma_next}, io, blend, stream);
 }
 
 }  // namespace
 
+// The plain DDIM step is the kernel inside the benchmarked, graph-captured denoise step, and has always run one element per thread:
+// vec_ok = false keeps it so whatever the alignment (the 16-byte form gives the same bits; the timed region is not this entry
+// point's to change).  Every other entry point lets run_cfg_step choose.
 extern "C" int af_cfg_ddim_step(const void* eps2, const void* x, void* x_prev, void* pred_x0, int64_t n, int has_uncond,
                                 float guidance, float a_t, float a_prev, void* stream) {
-  AF_REQUIRE(eps2 && x && x_prev && n > 0, "af_cfg_ddim_step: bad argument");
-  AF_REQUIRE(a_t > 0.f && a_t <= 1.f && a_prev > 0.f && a_prev <= 1.f, "af_cfg_ddim_step: alphas must be in (0, 1]");
-  const DdimCoefs k = ddim_coefs(guidance, a_t, a_prev);
-  AfLaunchScope scope(AF_FAM_ELEM, stream);
-  hipLaunchKernelGGL((cfg_ddim_kernel<BLEND_NONE, false>), grid1d(n), dim3(256), 0, (hipStream_t)stream, (const float*)eps2,
-                     (const float*)x, (float*)x_prev, (float*)pred_x0, (long)n, has_uncond, k, InpaintBlend{});
-  return af_check_launch("af_cfg_ddim_step");
+  return ddim_step("af_cfg_ddim_step", {eps2, x, {}, x_prev, pred_x0, n, has_uncond, guidance}, a_t, a_prev, nullptr, stream, false);
 }
 
 extern "C" int af_cfg_ddim_inpaint_step(const void* eps2, const void* x, void* x_prev, void* pred_x0, int64_t n, int has_uncond,
                                         float guidance, float a_t, float a_prev, const void* z, const void* noise, const void* mask,
                                         int B_img, int B_mask, int64_t hw, float sa_next, float sb_next, void* stream) {
-  AF_REQUIRE(eps2 && x && x_prev && n > 0, "af_cfg_ddim_inpaint_step: bad argument");
-  AF_REQUIRE(a_t > 0.f && a_t <= 1.f && a_prev > 0.f && a_prev <= 1.f, "af_cfg_ddim_inpaint_step: alphas must be in (0, 1]");
-  InpaintBlend bl;
-  if (int rc = make_blend("af_cfg_ddim_inpaint_step", n, z, noise, mask, B_img, B_mask, hw, sa_next, sb_next, bl)) return rc;
-  const DdimCoefs k = ddim_coefs(guidance, a_t, a_prev);
-  AfLaunchScope scope(AF_FAM_ELEM, stream);
-  launch_blend(false, n, {eps2, x, x_prev, pred_x0}, bl, [&](auto, auto v4, auto blend, dim3 grid) {
-    hipLaunchKernelGGL((cfg_ddim_kernel<blend, v4>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2, (const float*)x,
-                       (float*)x_prev, (float*)pred_x0, (long)n, has_uncond, k, bl);
-  });
-  return af_check_launch("af_cfg_ddim_inpaint_step");
+  const BlendArgs blend{z, noise, mask, B_img, B_mask, hw, sa_next, sb_next};
+  return ddim_step("af_cfg_ddim_inpaint_step", {eps2, x, {}, x_prev, pred_x0, n, has_uncond, guidance}, a_t, a_prev, &blend, stream,
+                   true);
 }
-
-namespace {
-
-int dpmpp_check(const char* who, const void* eps2, const void* x, const void* x_base, const void* x0_prev, const void* x_out,
-                const void* x0_out, int64_t n, float guidance, float alpha_s, float sigma_s, float c_base, float c0, float c1) {
-  const std::string w(who);
-  AF_REQUIRE(eps2 && x && x_base && x_out && x0_out && n > 0, w + ": bad argument");
-  AF_REQUIRE(alpha_s > 0.f && alpha_s <= 1.f && sigma_s >= 0.f && sigma_s < 1.f, w + ": need alpha_s in (0, 1] and sigma_s in [0, 1)");
-  AF_REQUIRE(std::isfinite(guidance) && std::isfinite(c_base) && std::isfinite(c0) && std::isfinite(c1),
-             w + ": coefficients must be finite");
-  AF_REQUIRE(x0_prev || c1 == 0.f, w + ": x0_prev is NULL but c1 != 0");
-  return AF_OK;
-}
-
-}  // namespace
 
 extern "C" int af_cfg_dpmpp_step(const void* eps2, const void* x, const void* x_base, const void* x0_prev, void* x_out, void* x0_out,
                                  int64_t n, int has_uncond, float guidance, float alpha_s, float sigma_s, float c_base, float c0,
                                  float c1, void* stream) {
-  if (int rc = dpmpp_check("af_cfg_dpmpp_step", eps2, x, x_base, x0_prev, x_out, x0_out, n, guidance, alpha_s, sigma_s, c_base, c0, c1))
-    return rc;
-  const bool has_prev = c1 != 0.f;
-  const DpmppCoefs k{guidance, sigma_s, alpha_s, c_base, c0, c1};
-  AfLaunchScope scope(AF_FAM_ELEM, stream);
-  launch_flag_v4(has_prev, n, {eps2, x, x_base, x_out, x0_out, has_prev ? x0_prev : nullptr}, [&](auto prev, auto v4, dim3 grid) {
-    hipLaunchKernelGGL((cfg_dpmpp_kernel<prev, v4>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2, (const float*)x,
-                       (const float*)x_base, (const float*)x0_prev, (float*)x_out, (float*)x0_out, (long)n, has_uncond, k,
-                       InpaintBlend{});
-  });
-  return af_check_launch("af_cfg_dpmpp_step");
+  return dpmpp_step("af_cfg_dpmpp_step", {eps2, x, {x_base, x0_prev}, x_out, x0_out, n, has_uncond, guidance}, alpha_s, sigma_s,
+                    c_base, c0, c1, nullptr, stream);
 }
 
 extern "C" int af_cfg_dpmpp_inpaint_step(const void* eps2, const void* x, const void* x_base, const void* x0_prev, void* x_out,
                                          void* x0_out, int64_t n, int has_uncond, float guidance, float alpha_s, float sigma_s,
                                          float c_base, float c0, float c1, const void* z, const void* noise, const void* mask,
                                          int B_img, int B_mask, int64_t hw, float sa_next, float sb_next, void* stream) {
-  if (int rc = dpmpp_check("af_cfg_dpmpp_inpaint_step", eps2, x, x_base, x0_prev, x_out, x0_out, n, guidance, alpha_s, sigma_s, c_base,
-                           c0, c1))
-    return rc;
-  InpaintBlend bl;
-  if (int rc = make_blend("af_cfg_dpmpp_inpaint_step", n, z, noise, mask, B_img, B_mask, hw, sa_next, sb_next, bl)) return rc;
-  const bool has_prev = c1 != 0.f;
-  const DpmppCoefs k{guidance, sigma_s, alpha_s, c_base, c0, c1};
-  AfLaunchScope scope(AF_FAM_ELEM, stream);
-  launch_blend(has_prev, n, {eps2, x, x_base, x_out, x0_out, has_prev ? x0_prev : nullptr}, bl,
-               [&](auto prev, auto v4, auto blend, dim3 grid) {
-    hipLaunchKernelGGL((cfg_dpmpp_kernel<prev, v4, blend>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2,
-                       (const float*)x, (const float*)x_base, (const float*)x0_prev, (float*)x_out, (float*)x0_out, (long)n,
-                       has_uncond, k, bl);
-  });
-  return af_check_launch("af_cfg_dpmpp_inpaint_step");
+  const BlendArgs blend{z, noise, mask, B_img, B_mask, hw, sa_next, sb_next};
+  return dpmpp_step("af_cfg_dpmpp_inpaint_step", {eps2, x, {x_base, x0_prev}, x_out, x0_out, n, has_uncond, guidance}, alpha_s,
+                    sigma_s, c_base, c0, c1, &blend, stream);
 }
-
-namespace {
-
-int lcm_check(const char* who, const void* eps2, const void* x, const void* noise, const void* x_next, const void* denoised, int64_t n,
-              float guidance, float sqrt_a, float sqrt_1ma, float c_out, float c_skip, float sqrt_a_next, float sqrt_1ma_next) {
-  const std::string w(who);
-  AF_REQUIRE(eps2 && x && x_next && denoised && n > 0, w + ": bad argument");
-  AF_REQUIRE(sqrt_a > 0.f && sqrt_a <= 1.f && sqrt_1ma >= 0.f && sqrt_1ma < 1.f, w + ": need sqrt_a in (0, 1] and sqrt_1ma in [0, 1)");
-  AF_REQUIRE(std::isfinite(guidance) && std::isfinite(c_out) && std::isfinite(c_skip) && std::isfinite(sqrt_a_next) &&
-                 std::isfinite(sqrt_1ma_next),
-             w + ": coefficients must be finite");
-  AF_REQUIRE(!noise || (sqrt_a_next > 0.f && sqrt_a_next <= 1.f && sqrt_1ma_next >= 0.f && sqrt_1ma_next < 1.f),
-             w + ": need sqrt_a_next in (0, 1] and sqrt_1ma_next in [0, 1)");
-  return AF_OK;
-}
-
-}  // namespace
 
 extern "C" int af_cfg_lcm_step(const void* eps2, const void* x, const void* noise, void* x_next, void* denoised, int64_t n,
                                int has_uncond, float guidance, float sqrt_a, float sqrt_1ma, float c_out, float c_skip,
                                float sqrt_a_next, float sqrt_1ma_next, void* stream) {
-  if (int rc = lcm_check("af_cfg_lcm_step", eps2, x, noise, x_next, denoised, n, guidance, sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next,
-                         sqrt_1ma_next))
-    return rc;
-  const bool has_noise = noise != nullptr;
-  const LcmCoefs k{guidance, sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next, sqrt_1ma_next};
-  AfLaunchScope scope(AF_FAM_ELEM, stream);
-  launch_flag_v4(has_noise, n, {eps2, x, x_next, denoised, noise}, [&](auto has_nz, auto v4, dim3 grid) {
-    hipLaunchKernelGGL((cfg_lcm_kernel<has_nz, v4>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2, (const float*)x,
-                       (const float*)noise, (float*)x_next, (float*)denoised, (long)n, has_uncond, k, InpaintBlend{});
-  });
-  return af_check_launch("af_cfg_lcm_step");
+  return lcm_step("af_cfg_lcm_step", {eps2, x, {noise}, x_next, denoised, n, has_uncond, guidance}, sqrt_a, sqrt_1ma, c_out, c_skip,
+                  sqrt_a_next, sqrt_1ma_next, nullptr, stream);
 }
 
 extern "C" int af_cfg_lcm_inpaint_step(const void* eps2, const void* x, const void* noise, void* x_next, void* denoised, int64_t n,
@@ -563,19 +495,9 @@ extern "C" int af_cfg_lcm_inpaint_step(const void* eps2, const void* x, const vo
                                        float sqrt_a_next, float sqrt_1ma_next, const void* z, const void* blend_noise,
                                        const void* mask, int B_img, int B_mask, int64_t hw, float sa_next, float sb_next,
                                        void* stream) {
-  if (int rc = lcm_check("af_cfg_lcm_inpaint_step", eps2, x, noise, x_next, denoised, n, guidance, sqrt_a, sqrt_1ma, c_out, c_skip,
-                         sqrt_a_next, sqrt_1ma_next))
-    return rc;
-  InpaintBlend bl;
-  if (int rc = make_blend("af_cfg_lcm_inpaint_step", n, z, blend_noise, mask, B_img, B_mask, hw, sa_next, sb_next, bl)) return rc;
-  const bool has_noise = noise != nullptr;
-  const LcmCoefs k{guidance, sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next, sqrt_1ma_next};
-  AfLaunchScope scope(AF_FAM_ELEM, stream);
-  launch_blend(has_noise, n, {eps2, x, x_next, denoised, noise}, bl, [&](auto has_nz, auto v4, auto blend, dim3 grid) {
-    hipLaunchKernelGGL((cfg_lcm_kernel<has_nz, v4, blend>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)eps2,
-                       (const float*)x, (const float*)noise, (float*)x_next, (float*)denoised, (long)n, has_uncond, k, bl);
-  });
-  return af_check_launch("af_cfg_lcm_inpaint_step");
+  const BlendArgs blend{z, blend_noise, mask, B_img, B_mask, hw, sa_next, sb_next};
+  return lcm_step("af_cfg_lcm_inpaint_step", {eps2, x, {noise}, x_next, denoised, n, has_uncond, guidance}, sqrt_a, sqrt_1ma, c_out,
+                  c_skip, sqrt_a_next, sqrt_1ma_next, &blend, stream);
 }
 
 extern "C" int af_q_sample(const void* x0, const void* noise, const void* sa, const void* sb, void* xt, int B, int64_t per,

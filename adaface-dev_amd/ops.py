@@ -950,20 +950,28 @@ class InpaintBlend:
                 h * w, float(self.sa), float(self.sb)]
 
 
+def _cfg_step(kind: str, eps2: torch.Tensor, x: torch.Tensor, inputs, scalars, has_uncond: bool, blend: Optional[InpaintBlend]):
+    """The body of the three fused sampler steps: af_cfg_<kind>_step, or af_cfg_<kind>_inpaint_step with ``blend``, on eps2 fp32
+    [2n or n] and x fp32 [n].  ``inputs`` are the step's extra fp32 [n] streams in C-ABI order (None: passed as NULL),
+    ``scalars`` its coefficients after has_uncond.  Returns (new latent, x0-like output)."""
+    assert eps2.dtype == torch.float32 and x.dtype == torch.float32 and eps2.is_contiguous() and x.is_contiguous()
+    n = x.numel()
+    assert eps2.numel() == (2 * n if has_uncond else n)
+    for t in inputs:
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n)
+    out, aux = torch.empty_like(x), torch.empty_like(x)
+    name = f"af_cfg_{kind}_step" if blend is None else f"af_cfg_{kind}_inpaint_step"
+    args = [_p(eps2), _p(x), *(None if t is None else _p(t) for t in inputs), _p(out), _p(aux), n, int(has_uncond),
+            *(float(v) for v in scalars), *(() if blend is None else blend.args(x))]
+    _lib.check(getattr(_lib.lib(), name)(*args, _stream()), name)
+    return out, aux
+
+
 def cfg_ddim_step(eps2: torch.Tensor, x: torch.Tensor, guidance: float, a_t: float, a_prev: float, has_uncond: bool = True,
                   blend: Optional[InpaintBlend] = None):
     """eps2 fp32 [2n or n] = [e_cond ; e_uncond], x fp32 [n] -> (x_prev, pred_x0), ddim.py:253-302 (sigma = 0).  With ``blend``
     (x [B, 4, h, w]), x_prev is blended (af_cfg_ddim_inpaint_step); pred_x0 is not."""
-    assert eps2.dtype == torch.float32 and x.dtype == torch.float32 and eps2.is_contiguous() and x.is_contiguous()
-    n = x.numel()
-    assert eps2.numel() == (2 * n if has_uncond else n)
-    x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
-    args = [_p(eps2), _p(x), _p(x_prev), _p(pred_x0), n, int(has_uncond), float(guidance), float(a_t), float(a_prev)]
-    if blend is None:
-        _lib.check(_lib.lib().af_cfg_ddim_step(*args, _stream()), "af_cfg_ddim_step")
-    else:
-        _lib.check(_lib.lib().af_cfg_ddim_inpaint_step(*args, *blend.args(x), _stream()), "af_cfg_ddim_inpaint_step")
-    return x_prev, pred_x0
+    return _cfg_step("ddim", eps2, x, [], [guidance, a_t, a_prev], has_uncond, blend)
 
 
 def cfg_dpmpp_step(eps2: torch.Tensor, x: torch.Tensor, x_base: torch.Tensor, x0_prev: Optional[torch.Tensor], guidance: float,
@@ -972,21 +980,9 @@ def cfg_dpmpp_step(eps2: torch.Tensor, x: torch.Tensor, x_base: torch.Tensor, x0
     """eps2 fp32 [2n or n] = [e_cond ; e_uncond], x / x_base / x0_prev fp32 [n] -> (x_out, x0_out): one DPM-Solver++ step,
     x0 = (x - sigma_s e) / alpha_s, x_out = c_base x_base + c0 x0 + c1 x0_prev (x0_prev unused, may be None, when c1 == 0).
     With ``blend`` (x [B, 4, h, w]), x_out is blended (af_cfg_dpmpp_inpaint_step); x0_out is not."""
-    assert eps2.dtype == torch.float32 and x.dtype == torch.float32 and eps2.is_contiguous() and x.is_contiguous()
-    n = x.numel()
-    assert eps2.numel() == (2 * n if has_uncond else n)
-    assert x_base.dtype == torch.float32 and x_base.is_contiguous() and x_base.numel() == n
-    if c1 != 0.0:
-        assert x0_prev is not None and x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == n
-    x_out, x0_out = torch.empty_like(x), torch.empty_like(x)
-    prev = _p(x0_prev) if c1 != 0.0 else None
-    args = [_p(eps2), _p(x), _p(x_base), prev, _p(x_out), _p(x0_out), n, int(has_uncond), float(guidance), float(alpha_s),
-            float(sigma_s), float(c_base), float(c0), float(c1)]
-    if blend is None:
-        _lib.check(_lib.lib().af_cfg_dpmpp_step(*args, _stream()), "af_cfg_dpmpp_step")
-    else:
-        _lib.check(_lib.lib().af_cfg_dpmpp_inpaint_step(*args, *blend.args(x), _stream()), "af_cfg_dpmpp_inpaint_step")
-    return x_out, x0_out
+    assert x_base is not None and (c1 == 0.0 or x0_prev is not None)
+    return _cfg_step("dpmpp", eps2, x, [x_base, x0_prev if c1 != 0.0 else None], [guidance, alpha_s, sigma_s, c_base, c0, c1],
+                     has_uncond, blend)
 
 
 def cfg_lcm_step(eps2: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tensor], guidance: float, sqrt_a: float, sqrt_1ma: float,
@@ -996,19 +992,8 @@ def cfg_lcm_step(eps2: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tens
     x0 = (x - sqrt_1ma e) / sqrt_a, denoised = c_out x0 + c_skip x, x_next = sqrt_a_next denoised + sqrt_1ma_next noise
     (noise None: the last step, x_next = denoised).  With ``blend`` (x [B, 4, h, w]), x_next is blended
     (af_cfg_lcm_inpaint_step); denoised is not."""
-    assert eps2.dtype == torch.float32 and x.dtype == torch.float32 and eps2.is_contiguous() and x.is_contiguous()
-    n = x.numel()
-    assert eps2.numel() == (2 * n if has_uncond else n)
-    if noise is not None:
-        assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == n
-    x_next, denoised = torch.empty_like(x), torch.empty_like(x)
-    args = [_p(eps2), _p(x), None if noise is None else _p(noise), _p(x_next), _p(denoised), n, int(has_uncond), float(guidance),
-            float(sqrt_a), float(sqrt_1ma), float(c_out), float(c_skip), float(sqrt_a_next), float(sqrt_1ma_next)]
-    if blend is None:
-        _lib.check(_lib.lib().af_cfg_lcm_step(*args, _stream()), "af_cfg_lcm_step")
-    else:
-        _lib.check(_lib.lib().af_cfg_lcm_inpaint_step(*args, *blend.args(x), _stream()), "af_cfg_lcm_inpaint_step")
-    return x_next, denoised
+    return _cfg_step("lcm", eps2, x, [noise], [guidance, sqrt_a, sqrt_1ma, c_out, c_skip, sqrt_a_next, sqrt_1ma_next], has_uncond,
+                     blend)
 
 
 def q_sample(x0: torch.Tensor, noise: torch.Tensor, sa: torch.Tensor, sb: torch.Tensor) -> torch.Tensor:

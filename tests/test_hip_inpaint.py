@@ -57,7 +57,9 @@ def _step(kind, dev, e2, x, xb, xp, nz, has_uncond, blend):
 def test_inpaint_step_kernels(dev, kind, has_uncond, layout, bcast, last):
     """x_next is the plain kernel's output bit for bit where the mask is 1 and the fp32 known latent where it is 0 (fma(sb, noise,
     sa z) rounded once from fp64, or z on the last step); the x0 output is the plain kernel's everywhere.  Layouts: hw = 15 (scalar,
-    hw % 4 != 0), hw = 48 aligned (16-byte form), hw = 48 with every tensor one float off alignment (scalar)."""
+    hw % 4 != 0), hw = 48 aligned (16-byte form), hw = 48 with every tensor one float off alignment (scalar).  The offset layout also
+    runs the same data aligned, and both outputs equal the offset run's bit for bit: with the blend (scalar against 16-byte form)
+    and without it (DPM-Solver++ and LCM scalar against 16-byte; the plain DDIM step runs scalar either way)."""
     from adaface_dev_amd import ops
     B, (B_img, B_mask) = 3, bcast
     h, w = (3, 5) if layout == "scalar_hw" else (6, 8)
@@ -75,6 +77,15 @@ def test_inpaint_step_kernels(dev, kind, has_uncond, layout, bcast, last):
     blend = ops.InpaintBlend(D(z), None if last else D(n_fwd), D(m), sa, sb)
     y, x0 = _step(kind, dev, *args, has_uncond, blend)
     y_ref, x0_ref = _step(kind, dev, *args, has_uncond, None)
+    if off:
+        A = lambda t: _on(dev, t, False)
+        args_a = (A(e2), A(x), A(xb), A(xp), A(nz))
+        blend_a = ops.InpaintBlend(A(z), None if last else A(n_fwd), A(m), sa, sb)
+        assert all(t.data_ptr() % 16 == 0 for t in args_a + (blend_a.z, blend_a.mask)) and args[1].data_ptr() % 16 == 4
+        for (y_o, x0_o), b in (((y, x0), blend_a), ((y_ref, x0_ref), None)):
+            y_a, x0_a = _step(kind, dev, *args_a, has_uncond, b)
+            assert y_a.data_ptr() % 16 == 0 and x0_a.data_ptr() % 16 == 0
+            assert torch.equal(y_a, y_o) and torch.equal(x0_a, x0_o)
     y, x0, y_ref, x0_ref = (t.cpu() for t in (y, x0, y_ref, x0_ref))
     zb = z[torch.arange(B) % B_img]
     mb = m[torch.arange(B) % B_mask].expand(shp).bool()
