@@ -35,7 +35,7 @@ EXPORTS = (
     "af_splitk_reduce", "af_groupnorm_splitk_ok", "af_groupnorm_splitk", "af_xattn_chain",
     "af_image_u8_to_nhwc_f16", "af_vae_latents_q_sample", "af_cfg_dpmpp_step", "af_cfg_lcm_step",
     "af_cfg_ddim_inpaint_step", "af_cfg_dpmpp_inpaint_step", "af_cfg_lcm_inpaint_step", "af_vae_latents_z_q_sample",
-    "af_vae_attention", "af_latent_resize_q_sample",
+    "af_vae_attention", "af_latent_resize_q_sample", "af_affine_prelu_ch", "af_face_align_crop",
 )
 
 
@@ -182,6 +182,8 @@ def lib() -> C.CDLL:
     L.af_scale_f32.argtypes = [vp, f32, i64, vp]
     L.af_clamp_f32.argtypes = [vp, f32, f32, i64, vp]
     L.af_affine_prelu.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp]
+    L.af_affine_prelu_ch.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp]
+    L.af_face_align_crop.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.af_maxpool2x2.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.af_global_avgpool.argtypes = [vp, vp, i32, i32, i32, vp]
     L.af_se_residual_prelu.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]

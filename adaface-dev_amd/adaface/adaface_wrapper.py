@@ -195,7 +195,7 @@ class AdaFaceWrapper(nn.Module):
                  num_inference_steps=50, subject_string="z", negative_prompt=None, max_prompt_length=77,
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
-                 lcm_lora_path=None, lcm_lora_scale=1.0):
+                 lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None):
         super().__init__()
         if pipeline_name not in ("text2img", "img2img", "inpaint", None):
             raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img, img2img and inpaint paths (and None = face "
@@ -237,7 +237,10 @@ class AdaFaceWrapper(nn.Module):
         ccfg = clip_config or clip_text_config()
         self.tokenizer = tokenizer or WordTokenizer(ccfg.vocab_size)
         self.text_encoder = text_encoder or CLIPTextModelWrapper(ccfg)
-        self.id2ada_prompt_encoder = id2ada_prompt_encoder or Arc2Face_ID2AdaPrompt(clip_config=ccfg)
+        # face_id_extractor (adaface/face_align.py FaceIDExtractor): prepare_adaface_embeddings(image_paths) then extracts the IDs itself
+        self.id2ada_prompt_encoder = id2ada_prompt_encoder or Arc2Face_ID2AdaPrompt(clip_config=ccfg, face_id_extractor=face_id_extractor)
+        if face_id_extractor is not None and id2ada_prompt_encoder is not None:
+            id2ada_prompt_encoder.face_id_extractor = face_id_extractor
         if adaface_encoder_cfg_scales is not None:
             self.id2ada_prompt_encoder.out_id_embs_cfg_scale = adaface_encoder_cfg_scales[0]
         self.encoders_num_id_vecs = [self.id2ada_prompt_encoder.num_id_vecs]

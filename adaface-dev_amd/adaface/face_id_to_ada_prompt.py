@@ -4,7 +4,8 @@
 
 The 512-d face-ID vector comes from insightface's ONNX detector/recogniser in the reference (third-party, CPU
 round-trips); here it is an input (or, as the reference itself does when no image is given,
-``torch.randn(bs, 512)``, :384).  ConsistentID / Joint encoders are out of scope (external package not in the tree)."""
+``torch.randn(bs, 512)``, :384), or it is extracted from images by a ``face_id_extractor`` (``adaface/face_align.py``:
+the caller's detector, the fused align-crop kernel and IResNet) when one is configured.  ConsistentID / Joint encoders are out of scope (external package not in the tree)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -19,8 +20,10 @@ class Arc2Face_ID2AdaPrompt(nn.Module):
 
     def __init__(self, subj_basis_generator=None, text_to_image_prompt_encoder=None, out_id_embs_cfg_scale=1.0,
                  num_static_img_suffix_embs=0, clip_config=None, tokenizer=None, subject_string="z", adaface_ckpt_path=None,
-                 extend_prompt2token_proj_attention_multiplier=1, prompt2token_proj_ext_attention_perturb_ratio=0.1):
+                 extend_prompt2token_proj_attention_multiplier=1, prompt2token_proj_ext_attention_perturb_ratio=0.1,
+                 face_id_extractor=None):
         super().__init__()
+        self.face_id_extractor = face_id_extractor          # a face_align.FaceIDExtractor, or None: IDs are then an input only
         self.subject_string = subject_string
         self.output_dim = 768
         self.extend_prompt2token_proj_attention_multiplier = extend_prompt2token_proj_attention_multiplier
@@ -99,8 +102,16 @@ class Arc2Face_ID2AdaPrompt(nn.Module):
 
     def get_img_prompt_embs(self, init_id_embs, pre_clip_features=None, image_paths=None, image_objs=None, id_batch_size=1,
                             skip_non_faces=True, avg_at_stage=None, perturb_at_stage=None, perturb_std=0.0, verbose=False):
+        faceless_img_count = 0
         if image_paths is not None or image_objs is not None:
-            raise NotImplementedError("face detection / ID extraction from images uses insightface ONNX (third-party, absent)")
+            if self.face_id_extractor is None:
+                raise NotImplementedError("face detection / ID extraction from images uses insightface ONNX (third-party, absent)")
+            if init_id_embs is None:                      # IDs handed in together with images win
+                images = image_paths if image_paths is not None else image_objs
+                faceless_img_count, init_id_embs = self.face_id_extractor.extract(images, calc_avg=(avg_at_stage == "id_emb"),
+                                                                                 skip_non_faces=skip_non_faces)
+                if init_id_embs is None:
+                    return faceless_img_count, None, None, None
         dev = next(self.text_to_image_prompt_encoder.parameters()).device
         if init_id_embs is None:
             faceid_embeds = torch.randn(id_batch_size, 512).to(device=dev, dtype=torch.float16)        # reference :384
@@ -117,7 +128,7 @@ class Arc2Face_ID2AdaPrompt(nn.Module):
             faceid_embeds = faceid_embeds.mean(dim=0, keepdim=True)
         if perturb_at_stage == "img_prompt_emb" and perturb_std > 0:
             pos_prompt_embs = perturb_tensor(pos_prompt_embs, perturb_std, perturb_std_is_relative=True, keep_norm=True)
-        return 0, faceid_embeds, pos_prompt_embs, None
+        return faceless_img_count, faceid_embeds, pos_prompt_embs, None
 
     @staticmethod
     def average_id_embs(face_id_embs):
@@ -137,8 +148,11 @@ class Arc2Face_ID2AdaPrompt(nn.Module):
             # the 'id_emb' stage -- the reference averages there only while it extracts IDs from images (calc_avg, :325-350;
             # ``average_id_embs`` below is that step for callers that bring pre-extracted IDs of several images)
             bs = 1 if avg is not None else (face_id_embs.shape[0] if face_id_embs is not None else 1)
-            _, _, img_prompt_embs, _ = self.get_img_prompt_embs(face_id_embs, None, None, None, bs, perturb_at_stage=perturb_at_stage,
-                                                                perturb_std=perturb_std, avg_at_stage=avg)
+            # images are routed down only while there is no ID to go by: face_id_embs given together with images wins
+            _, _, img_prompt_embs, _ = self.get_img_prompt_embs(face_id_embs, None, image_paths if face_id_embs is None else None, None, bs,
+                                                                perturb_at_stage=perturb_at_stage, perturb_std=perturb_std, avg_at_stage=avg)
+            if img_prompt_embs is None:                    # images were given and none of them shows a face
+                return None, None, lens
         elif avg is not None:
             img_prompt_embs = img_prompt_embs.mean(dim=0, keepdim=True)
         embs = self.subj_basis_generator(img_prompt_embs, clip_features=None, raw_id_embs=None,

@@ -6,6 +6,8 @@
 //   af_maxpool2x2        2x2 / stride 2 max
 //   af_global_avgpool    mean over H*W per (b, c)                    (SE squeeze)
 //   af_se_residual_prelu y = prelu(x * sigmoid(s[b,c]) + residual)   (SE excite + shortcut + PReLU in one pass)
+//   af_affine_prelu_ch   the same with one PReLU slope per channel  (IResNet, insightface's recogniser: nn.PReLU(planes))
+//   af_face_align_crop   uint8 photo -> F aligned fp16 crops: inverse similarity warp, bilinear, (v - 127.5) / 127.5, 8-channel NHWC
 // and their input-gradient kernels (the encoder is frozen -- arcface_wrapper.py:65-76 -- but the alignment loss differentiates
 // THROUGH it into the decoded image, ddpm.py:2511-2535, so only d/dx is ever needed, never a parameter gradient):
 //   af_affine_prelu_bwd       dx = dy * prelu'(x * scale + shift) * scale
@@ -34,6 +36,56 @@ __global__ __launch_bounds__(256) void affine_prelu_kernel(const half_t* __restr
     o[e] = (half_t)prelu(f, sl);
   }
   *reinterpret_cast<half8_t*>(y + i * 8) = o;
+}
+
+__global__ __launch_bounds__(256) void affine_prelu_ch_kernel(const half_t* __restrict__ x, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, const float* __restrict__ slope,
+                                                              half_t* __restrict__ y, long n8, int C8) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  const int c0 = (int)(i % C8) * 8;
+  const half8_t v = *reinterpret_cast<const half8_t*>(x + i * 8);
+  half8_t o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float f = (float)v[e];
+    if (scale) f = f * scale[c0 + e] + shift[c0 + e];
+    o[e] = (half_t)(slope ? prelu(f, slope[c0 + e]) : f);
+  }
+  *reinterpret_cast<half8_t*>(y + i * 8) = o;
+}
+
+// One thread per output pixel of one face: (sx, sy) = inv[f] . (x, y, 1) in integer pixel coordinates (cv2.warpAffine's convention, no
+// half-pixel shift), bilinear over the four neighbours with a tap outside the image counted as 0 (BORDER_CONSTANT 0: continuous across the
+// edge), fp32 throughout, one 16-byte store.  A source point whose four taps are all outside (NaN / Inf coordinates included) never
+// forms an address.
+__global__ __launch_bounds__(256) void face_align_crop_kernel(const unsigned char* __restrict__ img, const float* __restrict__ inv,
+                                                              half_t* __restrict__ out, int H, int W, int size, long npix) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= npix) return;
+  const int x = (int)(i % size), y = (int)((i / size) % size);
+  const float* m = inv + (i / ((long)size * size)) * 6;
+  const float sx = m[0] * (float)x + m[1] * (float)y + m[2], sy = m[3] * (float)x + m[4] * (float)y + m[5];
+  float v[3] = {0.f, 0.f, 0.f};
+  if (sx > -1.f && sx < (float)W && sy > -1.f && sy < (float)H) {
+    const float fx0 = floorf(sx), fy0 = floorf(sy);
+    const int x0 = (int)fx0, y0 = (int)fy0;                  // in [-1, W - 1] x [-1, H - 1]
+    const float ax = sx - fx0, ay = sy - fy0;
+    const float wgt[4] = {(1.f - ay) * (1.f - ax), (1.f - ay) * ax, ay * (1.f - ax), ay * ax};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int xx = x0 + (t & 1), yy = y0 + (t >> 1);
+      if (xx >= 0 && xx < W && yy >= 0 && yy < H) {
+        const unsigned char* p = img + (yy * W + xx) * 3;    // H * W * 3 < 2^31 (checked by the caller)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] += wgt[t] * (float)p[c];
+      }
+    }
+  }
+  half8_t o = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c] = (half_t)((v[c] - 127.5f) / 127.5f);
+  *reinterpret_cast<half8_t*>(out + i * 8) = o;
 }
 
 __global__ __launch_bounds__(256) void maxpool2x2_kernel(const half_t* __restrict__ x, half_t* __restrict__ y, int Ho, int Wo,
@@ -228,6 +280,31 @@ extern "C" int af_affine_prelu(const void* x, const void* scale, const void* shi
   hipLaunchKernelGGL(affine_prelu_kernel, g1(n8), dim3(256), 0, (hipStream_t)stream, (const half_t*)x, (const float*)scale,
                      (const float*)shift, (const float*)slope, (half_t*)y, n8, C / 8);
   return af_check_launch("af_affine_prelu");
+}
+
+extern "C" int af_affine_prelu_ch(const void* x, const void* scale, const void* shift, const void* slope, void* y, int64_t rows, int C,
+                                  void* stream) {
+  AF_REQUIRE(x && y && rows > 0 && C > 0 && C % 8 == 0, "af_affine_prelu_ch: C must be a positive multiple of 8");
+  AF_REQUIRE((scale == nullptr) == (shift == nullptr), "af_affine_prelu_ch: scale and shift go together");
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  const long n8 = rows * (C / 8);
+  hipLaunchKernelGGL(affine_prelu_ch_kernel, g1(n8), dim3(256), 0, (hipStream_t)stream, (const half_t*)x, (const float*)scale,
+                     (const float*)shift, (const float*)slope, (half_t*)y, n8, C / 8);
+  return af_check_launch("af_affine_prelu_ch");
+}
+
+extern "C" int af_face_align_crop(const void* image_u8, const void* inv_mats, void* out, int H, int W, int F, int size, void* stream) {
+  AF_REQUIRE(image_u8 && inv_mats && out && H > 0 && W > 0, "af_face_align_crop: bad argument");
+  AF_REQUIRE((long)H * W * 3 < (1L << 31), "af_face_align_crop: the image needs fewer than 2^31 bytes (H * W * 3)");
+  AF_REQUIRE(F >= 1, "af_face_align_crop: at least one face");
+  AF_REQUIRE(size == 112 || size == 128, "af_face_align_crop: size must be 112 or 128");
+  AF_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "af_face_align_crop: out must be 16-byte aligned");
+  const long npix = (long)F * size * size;
+  AF_REQUIRE(npix < (1L << 31), "af_face_align_crop: needs fewer than 2^31 output pixels");
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  hipLaunchKernelGGL(face_align_crop_kernel, g1(npix), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)image_u8,
+                     (const float*)inv_mats, (half_t*)out, H, W, size, npix);
+  return af_check_launch("af_face_align_crop");
 }
 
 extern "C" int af_maxpool2x2(const void* x, void* y, int B, int Ho, int Wo, int C, void* stream) {

@@ -1281,6 +1281,42 @@ def affine_prelu(x, scale=None, shift=None, slope=None):
     return y
 
 
+def affine_prelu_ch(x, scale=None, shift=None, slope=None):
+    """``affine_prelu`` with one PReLU slope per channel (slope fp32 [C], nn.PReLU(C)): IResNet's activations."""
+    _chk_f16(x, "affine_prelu_ch.x")
+    Cn = x.shape[-1]
+    for name, t in (("scale", scale), ("shift", shift), ("slope", slope)):
+        if t is not None and (t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() or tuple(t.shape) != (Cn,)):
+            raise RuntimeError(f"affine_prelu_ch.{name}: expected contiguous fp32 ({Cn},) on {x.device}, got {t.dtype} {tuple(t.shape)} "
+                               f"on {t.device}")
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib().af_affine_prelu_ch(_p(x), _p(scale), _p(shift), _p(slope), _p(y), x.numel() // Cn, Cn, _stream()),
+               "af_affine_prelu_ch")
+    return y
+
+
+def face_align_crop(image_u8, inv_mats, size=112):
+    """uint8 RGB photo [H, W, 3] + inverse similarity matrices fp32 [F, 2, 3] (crop -> image) -> the recogniser's input, fp16
+    [F, size, size, 8]: bilinear, cv2.warpAffine's pixel convention, outside the image = 0, (v - 127.5) / 127.5 in channels 0-2, zeros in
+    3-7.  One launch per image (af_face_align_crop)."""
+    if image_u8.dtype != torch.uint8 or not image_u8.is_cuda or not image_u8.is_contiguous():
+        raise RuntimeError(f"face_align_crop: expected a contiguous uint8 device tensor, got {image_u8.dtype} {image_u8.device} "
+                           f"contiguous={image_u8.is_contiguous()}")
+    if image_u8.dim() != 3 or image_u8.shape[2] != 3:
+        raise RuntimeError(f"face_align_crop: expected [H, W, 3], got {tuple(image_u8.shape)}")
+    if (inv_mats.dtype != torch.float32 or inv_mats.device != image_u8.device or not inv_mats.is_contiguous() or inv_mats.dim() != 3
+            or tuple(inv_mats.shape[1:]) != (2, 3)):
+        raise RuntimeError(f"face_align_crop.inv_mats: expected contiguous fp32 [F, 2, 3] on {image_u8.device}, got {inv_mats.dtype} "
+                           f"{tuple(inv_mats.shape)} on {inv_mats.device}")
+    H, W, _ = image_u8.shape
+    nf, size = inv_mats.shape[0], int(size)
+    if size not in (112, 128):                       # (before the allocation: the C ABI refuses it too)
+        raise RuntimeError(f"face_align_crop: size must be 112 or 128, got {size}")
+    out = torch.empty((nf, size, size, 8), dtype=F16, device=image_u8.device)
+    _lib.check(_lib.lib().af_face_align_crop(_p(image_u8), _p(inv_mats), _p(out), H, W, nf, size, _stream()), "af_face_align_crop")
+    return out
+
+
 def maxpool2x2(x):
     B, H2, W2, Cn = x.shape
     y = torch.empty((B, H2 // 2, W2 // 2, Cn), dtype=F16, device=x.device)

@@ -506,6 +506,14 @@ int af_prefetch_ex(const void* ptr, int64_t bytes, int max_workgroups, void* str
  * NHWC fp16 activations, C % 8 == 0.  Convolutions / FCs are af_gemm calls with eval-mode BatchNorm folded on the host.
  * y = prelu(x * scale[c] + shift[c]); scale/shift fp32 [C] or both NULL; slope fp32 [1] device pointer or NULL (no PReLU) */
 int af_affine_prelu(const void* x, const void* scale, const void* shift, const void* slope, void* y, int64_t rows, int C, void* stream);
+/* the same with one slope per channel: slope fp32 [C] or NULL (IResNet, insightface's recogniser: nn.PReLU(planes)) */
+int af_affine_prelu_ch(const void* x, const void* scale, const void* shift, const void* slope, void* y, int64_t rows, int C, void* stream);
+/* 5-point face alignment into the recogniser's crop, one launch per image: image_u8 uint8 RGB [H, W, 3] contiguous, inv_mats fp32
+ * [F, 2, 3] (crop -> image), out fp16 [F, size, size, 8] (16-byte aligned).  Output pixel (x, y) of face f samples the image at
+ * (sx, sy) = inv_mats[f] . (x, y, 1): integer pixel coordinates without a half-pixel shift (cv2.warpAffine's convention), bilinear over the
+ * four neighbours, a tap outside the image counts as 0 (BORDER_CONSTANT 0).  Channels 0-2 = (v - 127.5) / 127.5 in RGB order, fp32
+ * arithmetic rounded once; channels 3-7 are written as 0.  size in {112, 128}, F >= 1, H * W * 3 < 2^31, F * size^2 < 2^31.          */
+int af_face_align_crop(const void* image_u8, const void* inv_mats, void* out, int H, int W, int F, int size, void* stream);
 /* x [B, 2Ho, 2Wo, C] -> y [B, Ho, Wo, C] (nn.MaxPool2d(2, 2), arcface_resnet.py:165) */
 int af_maxpool2x2(const void* x, void* y, int B, int Ho, int Wo, int C, void* stream);
 /* x [B, HW, C] -> out fp16 [B, C] (AdaptiveAvgPool2d(1), arcface_resnet.py:142) */
