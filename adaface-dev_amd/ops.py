@@ -1317,6 +1317,120 @@ def face_align_crop(image_u8, inv_mats, size=112):
     return out
 
 
+# ----------------------------------------------------------------------------- RetinaFace detector (af_detect.hip)
+RETINA_CAPACITY = 1024              # candidates per image af_retina_nms holds in LDS
+RETINA_STEPS = (8, 16, 32)
+RETINA_MIN_SIZES = ((16.0, 32.0), (64.0, 128.0), (256.0, 512.0))
+STEM_COLS = 160                     # 7 * 7 * 3 = 147 columns of the stem's im2col rows, zero-padded to a multiple of 8
+
+
+def _chk_nhwc(t, name):
+    _chk_f16(t, name)
+    if t.dim() != 4 or t.shape[3] % 8 or t.numel() == 0:
+        raise RuntimeError(f"{name}: expected a non-empty NHWC tensor with C % 8 == 0, got {tuple(t.shape)}")
+
+
+def stem_im2col7x7(images_u8, scale, shift, bgr=False):
+    """uint8 RGB photos [B, H, W, 3] -> (fp16 rows [B * Ho * Wo, 160] of the 7x7 / stride 2 / pad 3 stem over the image padded to multiples
+    of 32, (Ho, Wo)); columns (ky, kx, c) = v * scale[c] + shift[c], a tap outside the image 0, columns 147-159 zero (af_stem_im2col7x7).
+    scale, shift: three floats each."""
+    if images_u8.dtype != torch.uint8 or not images_u8.is_cuda or not images_u8.is_contiguous():
+        raise RuntimeError(f"stem_im2col7x7: expected a contiguous uint8 device tensor, got {images_u8.dtype} {images_u8.device} "
+                           f"contiguous={images_u8.is_contiguous()}")
+    if images_u8.dim() != 4 or images_u8.shape[3] != 3 or images_u8.numel() == 0:
+        raise RuntimeError(f"stem_im2col7x7: expected [B, H, W, 3], got {tuple(images_u8.shape)}")
+    scale, shift = [float(v) for v in scale], [float(v) for v in shift]
+    if len(scale) != 3 or len(shift) != 3:
+        raise RuntimeError("stem_im2col7x7: scale and shift take three values each")
+    B, H, W, _ = images_u8.shape
+    Ho, Wo = round_up(H, 32) // 2, round_up(W, 32) // 2
+    if B * H * W * 3 >= 1 << 31 or B * Ho * Wo * STEM_COLS * 2 >= 1 << 31:           # (before the allocation: the C ABI refuses it too)
+        raise RuntimeError(f"stem_im2col7x7: {tuple(images_u8.shape)} needs 2^31 bytes or more in one operand; split the batch")
+    out = torch.empty((B * Ho * Wo, STEM_COLS), dtype=F16, device=images_u8.device)
+    f3 = C.c_float * 3
+    _lib.check(_lib.lib().af_stem_im2col7x7(_p(images_u8), f3(*scale), f3(*shift), _p(out), B, H, W, int(bool(bgr)), _stream()),
+               "af_stem_im2col7x7")
+    return out, (Ho, Wo)
+
+
+def relu_maxpool3x3s2(x):
+    """relu(max_pool2d(x, 3, 2, 1)) on NHWC fp16."""
+    _chk_nhwc(x, "relu_maxpool3x3s2.x")
+    B, H, W, Cn = x.shape
+    y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cn), dtype=F16, device=x.device)
+    _lib.check(_lib.lib().af_relu_maxpool3x3s2(_p(x), _p(y), B, H, W, Cn, _stream()), "af_relu_maxpool3x3s2")
+    return y
+
+
+def subsample2x(x):
+    """x[:, ::2, ::2, :] as a contiguous NHWC tensor: what a stride-2 1x1 convolution reads."""
+    _chk_nhwc(x, "subsample2x.x")
+    B, H, W, Cn = x.shape
+    y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, Cn), dtype=F16, device=x.device)
+    _lib.check(_lib.lib().af_subsample2x(_p(x), _p(y), B, H, W, Cn, _stream()), "af_subsample2x")
+    return y
+
+
+def upsample2x_add(a, b):
+    """a [B, 2h, 2w, C] + nearest2x(b [B, h, w, C])."""
+    _chk_nhwc(a, "upsample2x_add.a")
+    _chk_nhwc(b, "upsample2x_add.b")
+    B, h, w, Cn = b.shape
+    if tuple(a.shape) != (B, 2 * h, 2 * w, Cn) or a.device != b.device:
+        raise RuntimeError(f"upsample2x_add: a must be [B, 2h, 2w, C] for b {tuple(b.shape)} on {b.device}, got {tuple(a.shape)} on {a.device}")
+    y = torch.empty_like(a)
+    _lib.check(_lib.lib().af_upsample2x_add(_p(a), _p(b), _p(y), B, h, w, Cn, _stream()), "af_upsample2x_add")
+    return y
+
+
+def retina_decode(heads, level_hw, conf_thr, capacity=RETINA_CAPACITY, steps=RETINA_STEPS, min_sizes=RETINA_MIN_SIZES):
+    """Three head tensors fp16 [B, Hk * Wk, 32] (per anchor 16 columns [box 4 | cls 2 | ldm 10]) -> (cand fp32 [B, capacity, 16], count
+    int32 [B]): the rows x1, y1, x2, y2, score, 10 landmark coordinates, anchor index of the anchors with score >= conf_thr, in pixels, in
+    no particular order (af_retina_decode; the rules are in include/adaface_hip.h).  count is the number that passed, also beyond capacity."""
+    if len(heads) != 3 or len(level_hw) != 3:
+        raise RuntimeError("retina_decode: three levels")
+    B = heads[0].shape[0]
+    for k, (hd, (hk, wk)) in enumerate(zip(heads, level_hw)):
+        _chk_f16(hd, f"retina_decode.heads[{k}]")
+        if tuple(hd.shape) != (B, hk * wk, 32) or hd.device != heads[0].device or hd.numel() == 0:
+            raise RuntimeError(f"retina_decode.heads[{k}]: expected [{B}, {hk * wk}, 32] on {heads[0].device}, got {tuple(hd.shape)} on {hd.device}")
+    capacity = int(capacity)
+    if not 1 <= capacity <= RETINA_CAPACITY:
+        raise RuntimeError(f"retina_decode: capacity must be in [1, {RETINA_CAPACITY}], got {capacity}")
+    cand = torch.empty((B, capacity, 16), dtype=torch.float32, device=heads[0].device)
+    count = torch.empty((B,), dtype=torch.int32, device=heads[0].device)
+    hw = (C.c_int * 6)(*[int(v) for pair in level_hw for v in pair])
+    st = (C.c_int * 3)(*[int(v) for v in steps])
+    ms = (C.c_float * 6)(*[float(v) for pair in min_sizes for v in pair])
+    _lib.check(_lib.lib().af_retina_decode(_p(heads[0]), _p(heads[1]), _p(heads[2]), hw, st, ms, B, float(conf_thr), _p(cand), _p(count),
+                                           capacity, _stream()), "af_retina_decode")
+    return cand, count
+
+
+def retina_nms(cand, count, nms_thr, max_det=64):
+    """Sort + greedy suppression of ``retina_decode``'s lists (af_retina_nms) and ONE device-to-host copy -> (table fp32 [B, max_det, 16] in
+    kept order, rows beyond ``kept`` zero; counts int32 [B, 2] = (kept, passing)), host tensors.  More passing anchors than the capacity:
+    RuntimeError (which of them made the list depends on scheduling, so it is never returned)."""
+    if cand.dtype != torch.float32 or not cand.is_cuda or not cand.is_contiguous() or cand.dim() != 3 or cand.shape[2] != 16:
+        raise RuntimeError(f"retina_nms.cand: expected contiguous fp32 [B, C, 16] on the device, got {cand.dtype} {tuple(cand.shape)} on {cand.device}")
+    B, cap, _ = cand.shape
+    if count.dtype != torch.int32 or count.device != cand.device or not count.is_contiguous() or tuple(count.shape) != (B,):
+        raise RuntimeError(f"retina_nms.count: expected contiguous int32 [{B}] on {cand.device}, got {count.dtype} {tuple(count.shape)} on {count.device}")
+    max_det = int(max_det)
+    if not 1 <= cap <= RETINA_CAPACITY or not 1 <= max_det <= cap:
+        raise RuntimeError(f"retina_nms: needs 1 <= max_det <= capacity <= {RETINA_CAPACITY}, got max_det {max_det}, capacity {cap}")
+    buf = torch.empty((B * max_det * 16 + B * 2,), dtype=torch.float32, device=cand.device)          # table | counts: one copy out
+    table, counts = buf[:B * max_det * 16], buf[B * max_det * 16:]
+    _lib.check(_lib.lib().af_retina_nms(_p(cand), _p(count), _p(table), _p(counts), B, cap, max_det, float(nms_thr), _stream()),
+               "af_retina_nms")
+    host = buf.cpu()
+    table, counts = host[:B * max_det * 16].reshape(B, max_det, 16), host[B * max_det * 16:].view(torch.int32).reshape(B, 2)
+    if int(counts[:, 1].max()) > cap:
+        raise RuntimeError(f"retina_nms: {int(counts[:, 1].max())} anchors passed the confidence threshold in one image, more than the "
+                           f"{cap} the detector keeps; raise the confidence threshold")
+    return table, counts
+
+
 def maxpool2x2(x):
     B, H2, W2, Cn = x.shape
     y = torch.empty((B, H2 // 2, W2 // 2, Cn), dtype=F16, device=x.device)

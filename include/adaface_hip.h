@@ -536,6 +536,41 @@ int af_se_gate_grad(const void* x, const void* se_logits, const void* residual, 
 int af_se_residual_prelu_bwd(const void* x, const void* se_logits, const void* residual, const void* slope, const void* dy,
                              const void* dpool, void* dx, void* dres, int B, int HW, int C, void* stream);
 
+/* ---- RetinaFace-R50 face detector (adaface/retinaface.py; biubug6 Pytorch_Retinaface cfg_re50): the layers between its GEMMs and the
+ * post-processing.  NHWC fp16 activations, C % 8 == 0, tensors 16-byte aligned.  Every argument check precedes any launch (AF_E_BADARG, the
+ * function named in af_last_error()); an operand whose byte offsets would reach 2^31 is refused.
+ *
+ * The stem's A operand: image_u8 uint8 RGB [B, H, W, 3] -> out fp16 [B * Ho * Wo, 160], the rows of the 7x7 / stride 2 / pad 3 convolution
+ * over the image padded at the bottom and right to (Hp, Wp) = (H, W) rounded up to multiples of 32 (so every FPN level is exactly twice the
+ * next): Ho = Hp / 2, Wo = Wp / 2.  Column (ky * 7 + kx) * 3 + c holds v * scale[c] + shift[c] of pixel (2 oy - 3 + ky, 2 ox - 3 + kx); a tap
+ * outside the H x W image (halo and padding alike) is 0 in NORMALISED space, which is why the normalisation cannot be folded into the
+ * weights.  Columns 147..159 are written as 0.  bgr != 0: output channel c reads image channel 2 - c.  scale, shift: HOST fp32 [3].        */
+int af_stem_im2col7x7(const void* image_u8, const float* scale, const float* shift, void* out, int B, int H, int W, int bgr, void* stream);
+/* y = relu(maxpool 3x3 / stride 2 / pad 1 (x)) (the two commute): x [B, H, W, C] -> y [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C].  Padding
+ * never wins the maximum. */
+int af_relu_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, void* stream);
+/* the even pixels: x [B, H, W, C] -> y [B, (H + 1) / 2, (W + 1) / 2, C], y[b, i, j] = x[b, 2i, 2j] (the A operand of a stride-2 1x1 convolution) */
+int af_subsample2x(const void* x, void* y, int B, int H, int W, int C, void* stream);
+/* y = a + nearest2x(b): a, y [B, 2h, 2w, C], b [B, h, w, C]; fp32 sum, rounded once (the FPN's top-down path) */
+int af_upsample2x_add(const void* a, const void* b, void* y, int B, int h, int w, int C, void* stream);
+/* Anchor decode + score filter.  head0..2: fp16 [B, Hk * Wk, 32], per anchor a in {0, 1} the 16 columns a * 16 + [box 4 | cls 2 | ldm 10].
+ * HOST arrays: level_hw int [6] = (H0, W0, H1, W1, H2, W2), steps int [3], min_sizes fp32 [6] = two per level.  One lane per anchor, anchor
+ * index = level offset + (i * Wk + j) * 2 + a (biubug6's PriorBox order).  In pixels, fp32, s = min_sizes[k][a]:
+ *   cx = (j + 0.5) step + 0.1 box0 s, cy = (i + 0.5) step + 0.1 box1 s, w = s exp(0.2 box2), h = s exp(0.2 box3),
+ *   x1 = cx - w / 2, y1 = cy - h / 2, x2 = x1 + w, y2 = y1 + h; landmark n = ((j + 0.5) step + 0.1 ldm[2n] s, (i + 0.5) step + 0.1 ldm[2n+1] s);
+ *   score = 1 / (1 + exp(cls0 - cls1)).
+ * An anchor with score >= conf_thr (NaN never passes) takes the next row of its image's list cand fp32 [B, C, 16] = x1, y1, x2, y2, score,
+ * 10 landmark coordinates, anchor index, through a (vector) atomic counter; count int32 [B] is zeroed by this call and ends as the number of
+ * PASSING anchors, also beyond the capacity C (1 <= C <= 1024; rows beyond it are dropped, which ones depends on scheduling).           */
+int af_retina_decode(const void* head0, const void* head1, const void* head2, const int* level_hw, const int* steps, const float* min_sizes,
+                     int B, float conf_thr, void* cand, void* count, int C, void* stream);
+/* Non-maximum suppression of af_retina_decode's lists, one workgroup per image, candidates in LDS: sorted by (score descending, anchor index
+ * ascending) -- a total order, so the result does not depend on the append order -- then greedily: a kept candidate suppresses every later
+ * one with IoU > nms_thr, IoU = inter / (area_a + area_b - inter) with plain widths (torchvision's rule, not biubug6's "+ 1").  out fp32
+ * [B, max_det, 16]: the first max_det kept rows in order, rows beyond `kept` zero; out_counts int32 [B, 2] = (kept, passing).
+ * 1 <= max_det <= C <= 1024.                                                                                                            */
+int af_retina_nms(const void* cand, const void* count, void* out, void* out_counts, int B, int C, int max_det, float nms_thr, void* stream);
+
 /* ---- trainable DoRA adapters on the U-Net's up_blocks.3 convolutions (adaface/diffusers_attn_lora_capture.py:541-591; peft
  * DoraConv2dLayer.forward: y = base(x) + (s - 1) * conv(xd, W) + s * scaling * B(A(xd)), xd = dropout(x)) ---------------------
  * out = y0 + u[c] * c2 + v[c] * lb   (fp16 [rows, C]; u = s - 1, v = s * scaling, fp32 [C]) */
