@@ -644,6 +644,15 @@ extern "C" int af_gemm(const af_gemm_desc* d, void* stream) {
     AF_REQUIRE((d->stride == 0 || d->stride == 1) && d->upsample == 0 && d->tap_shift == 0, "af_gemm: the K tail needs stride 1, no upsample, no tap_shift");
     AF_SUPPORTED((d->tile >= 7 && d->tile <= 15), "af_gemm: the K tail runs on the whole-line tiles 7 .. 13, 15 and the halo-resident tile 14 only");
   }
+  if (d->upsample == 3) {
+    // nearest x2 + 3x3 as four 2x2 phase convolutions (weights from the phase pack, K = 4 c1): the halo-resident kernel's phase form or nothing -- no
+    // other kernel reads that pack
+    AF_SUPPORTED(d->tile == 14 && af_gemm_halo_variant(d) == 4, "af_gemm: upsample = 3 (phase form) runs on tile 14 inside af_gemm_halo_variant's scope only");
+    AF_REQUIRE(d->zeros != nullptr, "af_gemm: zeros must be non-null");
+    AfLaunchScope scope(AF_FAM_GEMM, stream);
+    AF_SUPPORTED(af_gemm3_try_launch(d, 1, 11, (hipStream_t)stream) == 0, "af_gemm: upsample = 3 needs a 16-byte aligned output with ld_out % 8 == 0");
+    return af_check_launch("af_gemm(tile 14, phase form)");
+  }
   AF_REQUIRE(d->K == d->taps * (d->c1 + d->c2) + d->c3 + d->c4, "af_gemm: K != taps*(c1+c2) (+ c3 + c4)");
   const bool gnp = d->gn_partials != nullptr;
   if (gnp) {

@@ -58,6 +58,8 @@ struct Gemm3Dev {
   int wpf_coop;         // workgroups that share one weight tile and split its prefetch (min(tiles_m, 32))
   int patch_tx;         // halo-resident kernel, PATCH form (images wider than 64 pixels): 16 x 16-pixel tiles, patch_tx of them per image row, patch_tpi per image
   int patch_tpi;
+  int up2_cout;         // halo-resident kernel, phase form of the nearest-x2 convolution (af_gemm_desc.upsample = 3): Cout.  N = 4 Cout phase-major rows and
+                        // H / W / Ho / Wo / HoWo describe the LOW-res image the kernel walks on; M stays the number of output rows
 };
 
 constexpr int BK3 = 32;
@@ -103,7 +105,7 @@ __device__ __forceinline__ void glds16_sbase_masked(const half_t* sbase, unsigne
       "s_mov_b64 exec, %0"
       : "=&s"(keep)
       : "v"(voff), "v"(pix), "s"(sbase), "s"((unsigned)(size_t)lds_dst)
-      : "memory", "m0", "vcc");
+      : "memory", "m0", "vcc", "scc");
 #pragma clang diagnostic pop
 }
 
@@ -122,19 +124,34 @@ enum { E3_STD = 0, E3_GEGLU = 1, E3_SPLIT_T = 2 };
 
 // Epilogue shared by the ring kernel and the whole-line kernel: split-K partial tiles, or bias / row bias / activation / residual
 // (identical arithmetic to af_gemm.hip's standard epilogue), GEGLU, transposed-V split.  LDSB = bytes of LDS the main loop owned.
-template <int EPI, int NWM, int NWN, int TN, int LDSB, bool PATCH = false>
+template <int EPI, int NWM, int NWN, int TN, int LDSB, int ROWMAP = 0>     // ROWMAP: 0 = the tile's rows are consecutive output rows, 1 = PATCH, 2 = UP2
 __device__ __forceinline__ void gemm3_epilogue(const Gemm3Dev& p, floatx4 (&acc)[TN][4], char* af_smem, int tile_m, int tile_n, int wm, int wn,
                                                int fr, int fq, int tid, const float* lnst = nullptr) {
   constexpr int TM = 4, NW = NWM * NWN, BM = NWM * 64, BN = NWN * TN * 16;
   // PATCH (halo-resident kernel on images wider than 64 pixels): the tile's 256 rows are a 16 x 16-pixel patch of one image, local row q = pixel
   // (q >> 4, q & 15) of the patch; staged standard epilogue without split-K only (the host guarantees it)
+  constexpr bool PATCH = ROWMAP == 1, UP2 = ROWMAP == 2;
   int patch_m0 = 0;
   if constexpr (PATCH) {
     const int im = tile_m / p.patch_tpi, t = tile_m - im * p.patch_tpi;
     const int py = t / p.patch_tx, px = t - py * p.patch_tx;
     patch_m0 = (im * p.Ho + py * 16) * p.Wo + px * 16;
   }
-  auto tile_row = [&](int row) { return PATCH ? patch_m0 + (row >> 4) * p.Wo + (row & 15) : tile_m * BM + row; };
+  // UP2 (the phase form of the nearest-x2 convolution): the tile's 256 rows are whole rows of ONE low-res image (p.Ho x p.Wo, Wo a power of two) and its
+  // columns belong to ONE phase (py, px), phase = tile_n * BN / Cout: local row (y, x) of image b is output row (b * 2 Ho + 2 y + py) * 2 Wo + 2 x + px and
+  // column n' is output channel n' - phase * Cout (the bias is indexed by that channel); staged standard epilogue without split-K only
+  int up2_m0 = 0, up2_n0 = 0, up2_ws = 0;
+  if constexpr (UP2) {
+    const int l0 = tile_m * BM, b = l0 / p.HoWo, y0 = (l0 - b * p.HoWo) / p.Wo;
+    const int ph = (tile_n * BN) / p.up2_cout;
+    up2_n0 = ph * p.up2_cout;
+    up2_ws = 31 - __builtin_clz(p.Wo);
+    up2_m0 = ((b * 2 * p.Ho + 2 * y0 + (ph >> 1)) * 2 * p.Wo) + (ph & 1);
+  }
+  auto tile_row = [&](int row) {
+    if constexpr (UP2) return up2_m0 + (row >> up2_ws) * 4 * p.Wo + (row & (p.Wo - 1)) * 2;
+    else return PATCH ? patch_m0 + (row >> 4) * p.Wo + (row & 15) : tile_m * BM + row;
+  };
   if (lnst != nullptr) {
     // LayerNorm folded into this GEMM: acc = x . (gamma W)^T of the UN-normalised rows; LN(x) W^T = rstd * (acc - mean * colsum) (+ b + W beta,
     // which is the packed bias).  lnst[row] = (mean, rstd) of the tile's rows, written by the main loop's statistics waves.
@@ -243,7 +260,7 @@ __device__ __forceinline__ void gemm3_epilogue(const Gemm3Dev& p, floatx4 (&acc)
   constexpr int BNO = EPI == E3_GEGLU ? BN / 2 : BN;          // output columns of the tile
   constexpr int TS = BNO + 8;                                  // staging row stride (halves): 16 bytes of padding
   constexpr bool kCanStage = (EPI == E3_STD || EPI == E3_GEGLU) && (size_t)BM * TS * 2 <= (size_t)LDSB;
-  if (kCanStage && (PATCH || (p.stage_ok && !(p.ablate & 32)))) {
+  if (kCanStage && (ROWMAP != 0 || (p.stage_ok && !(p.ablate & 32)))) {
     __syncthreads();                                           // every wave is done reading the last ring slot
     half_t* T = reinterpret_cast<half_t*>(af_smem);
 #pragma unroll
@@ -283,7 +300,7 @@ __device__ __forceinline__ void gemm3_epilogue(const Gemm3Dev& p, floatx4 (&acc)
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[tn][tm][e];
             if (p.bias) {
-              const floatx4 bv = *reinterpret_cast<const floatx4*>(p.bias + n0);
+              const floatx4 bv = *reinterpret_cast<const floatx4*>(p.bias + n0 - up2_n0);
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] += bv[e];
             }
@@ -368,7 +385,7 @@ __device__ __forceinline__ void gemm3_epilogue(const Gemm3Dev& p, floatx4 (&acc)
       const int row = c / CPR, cc = c - row * CPR;
       const int m = tile_row(row), n = tile_n * BNO + cc * 8;
       if (m < p.M && n < ncols)
-        *reinterpret_cast<half8_t*>(p.out + (size_t)m * p.ld_out + n) = *reinterpret_cast<const half8_t*>(T + row * TS + cc * 8);
+        *reinterpret_cast<half8_t*>(p.out + (size_t)m * p.ld_out + n - up2_n0) = *reinterpret_cast<const half8_t*>(T + row * TS + cc * 8);
     }
     return;
   }
@@ -1425,11 +1442,25 @@ __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
 // TN_ = 4 (round 6, the VAE's channel counts: 128-multiples that are no 160-multiples): a 256 x 128 tile, 16 KB weight stages.  PATCH (images wider than 64
 // pixels: the VAE decoder's 128 / 256 / 512 levels): the tile is a 16 x 16-pixel patch of one image (halo 18 x 18 = 324 pixels, 41 pieces) instead of whole
 // image rows; everything else -- stages, hazards, MFMA order per output element -- as before.
-template <bool TAIL, int TN_ = 5, bool PATCH = false>             // TAIL: the K-concatenated 1x1 shortcut behind the chunks (its own instantiation: the plain kernel keeps its registers)
+//
+// UP2 (af_gemm_desc.upsample = 3): nearest-x2 + 3x3 as FOUR 2x2 phase convolutions of the low-res image.  After the upsample the nine taps of output pixel
+// (2 y + py, 2 x + px) read only the 2 x 2 low-res pixels {y + py - 1, y + py} x {x + px - 1, x + px}, so with the weights that fold onto one pixel summed in
+// advance (ops.pack_conv3x3_up2: rows [4 Cout] phase-major, K = (a, b, cin)) a chunk is FOUR stages instead of nine.  Geometrically this is the stride-1
+// kernel on the low-res image (the host passes H / W / Ho / Wo = the low-res size and N = 4 Cout): same tile, same halo, same gather.  What differs:
+//   * an N tile lies in one phase (Cout % 160 == 0), phase = tile_n / (Cout / 160); stage s = (a, b) of the chunk reads tap (py + a, px + b) of the 3 x 3
+//     low-res window -- 16 fragment-address registers, computed once from the phase;
+//   * four stages per chunk on a three-slot weight ring: the slot of a stage is no compile-time function of its tap.  The three slot offsets live in three
+//     scalars that rotate once per chunk (stage s of a chunk sits in slot s % 3 of the ROTATED order, also for s = 4, 5 = the next chunk's stages 0, 1 that the
+//     look-ahead fills), added to the two weight fragment bases: two vector adds per stage, no scalar load, no table;
+//   * the next chunk's halo (at most 43 pieces here = six per wave) goes out two pieces per stage under stages 0 .. 2;
+//   * the epilogue scatters the tile's rows to the phase's output pixels (gemm3_epilogue, UP2).
+// Stages, hazards, barriers, priorities and waits are the nine-tap loop's with the look-ahead taken modulo 4.
+template <bool TAIL, int TN_ = 5, bool PATCH = false, bool UP2 = false>   // TAIL: the K-concatenated 1x1 shortcut behind the chunks (its own instantiation: the plain kernel keeps its registers)
 __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
   constexpr int NWM = 4, NWN = 2, TN = TN_, TM = 4, NW = 8, BM = CH_BM, BN = NWN * TN * 16;
   constexpr int WSZ = BN * 128;                                  // one weight stage (CH_WSZ at TN = 5)
   static_assert(!(TAIL && (PATCH || TN_ != 5)), "the K tail exists in the 256 x 160 whole-rows form only");
+  static_assert(!(UP2 && (TAIL || PATCH || TN_ != 5)), "the phase form exists in the 256 x 160 whole-rows form only");
   constexpr int APW = (CH_NP_MAX + NW - 1) / NW;                 // 7 halo pieces per wave at most
   constexpr int WPW = (BN / 8 + NW - 1) / NW;                    // 3 weight pieces per wave at most (20 pieces; 2 of 16 at TN = 4)
   constexpr int WBASE = 2 * CH_ASZ;                              // the weight ring behind the two halo buffers
@@ -1531,9 +1562,9 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
       glds16_sbase_masked(src, (TAIL ? __umul24((unsigned)a_pix[j], (unsigned)ld2) : (unsigned)a_pix[j] * (unsigned)ld2) + chunk16, a_pix[j],
                           af_smem + buf_off + (wave + NW * j) * 1024);   // (TAIL: pixel index, row pitch < 2^24)
   };
-  auto issue_wk = [&](int k0, int sl) {                              // this wave's weight pieces of the stage whose first weight column is k0, ring slot sl
+  auto issue_wo = [&](int k0, int sl_off) {                          // this wave's weight pieces of the stage whose first weight column is k0, ring slot at byte sl_off
     const half_t* wb = wtr + (size_t)k0;
-    char* Ws = af_smem + WBASE + sl * WSZ;
+    char* Ws = af_smem + WBASE + sl_off;
 #pragma unroll
     for (int j = 0; j < WPW; ++j)
       if (wave + NW * j < BN / 8) {
@@ -1541,6 +1572,7 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
         else glds16_sbase(wb, w_off[j], Ws + (wave + NW * j) * 1024);
       }
   };
+  auto issue_wk = [&](int k0, int sl) { issue_wo(k0, sl * WSZ); };
   auto issue_w = [&](int u, int tap, int sl) { issue_wk(tap * Cin + u * 64, sl); };     // ... of the stage at (chunk u, tap)
   // K-tail stage t: the tile's 256 rows x 64 columns of a3 | a4 as 32 pieces of 8 rows (wave w: pieces w + 8 j, j < 4), row q at q * 128 of the buffer,
   // chunk index XOR (q & 7) = XOR prow: the same per-lane chunk as the halo pieces.  Every row is a valid output pixel (M % 256 == 0): no masking.
@@ -1586,15 +1618,21 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
   const int fr = lane & 15, fq = lane >> 4;
   // fragment addresses (bytes from af_smem), first K half; second half = address ^ 64 (chunk 4 + fq instead of fq under the XOR swizzle)
   const int wr0 = WBASE + (wn * TN * 16) * 128 + fr * 128 + ((fq ^ (fr >> 1)) * 16);
-  int fa[9][TM];
+  constexpr int NTAP = UP2 ? 4 : 9;                                  // stages per chunk
+  int up2_py = 0, up2_px = 0;                                        // UP2: the N tile's phase (workgroup-uniform)
+  if constexpr (UP2) {
+    const int ph = tile_n / (p.up2_cout / BN);
+    up2_py = ph >> 1, up2_px = ph & 1;
+  }
+  int fa[NTAP][TM];
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
     const int q = wm * 64 + tm * 16 + fr;
     const int r = fdiv(q, inv_wd), im = fdiv(r, inv_hi);
     const int hpb = im * blk_px + (r - im * Hi) * Wh + (q - r * Wd);
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int hp = hpb + (tap / 3) * Wh + (tap % 3);
+    for (int tap = 0; tap < NTAP; ++tap) {
+      const int hp = UP2 ? hpb + (up2_py + (tap >> 1)) * Wh + up2_px + (tap & 1) : hpb + (tap / 3) * Wh + (tap % 3);
       fa[tap][tm] = hp * 128 + ((fq ^ (hp & 7)) * 16);
     }
   }
@@ -1657,7 +1695,107 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 
-  if (grp == 0) {
+  if constexpr (UP2) {
+    int ws0 = 0, ws1 = WSZ, ws2 = 2 * WSZ;                           // ring slots (byte offsets) of the chunk's stages 0, 1, 2; stage 3 is in ws0 again, and the
+                                                                     // next chunk starts one slot on: the three rotate once per chunk
+#define CHU_SLOT(S) ((S) % 3 == 0 ? ws0 : ((S) % 3 == 1 ? ws1 : ws2))
+#define CHU_READ_FRAGS(T)                                                                                                        \
+  {                                                                                                                              \
+    const int wa_ = wr0 + CHU_SLOT(T), wb_ = (wr0 ^ 64) + CHU_SLOT(T);                                                           \
+    _Pragma("unroll") for (int tn = 0; tn < TN; ++tn) wf[tn] = *reinterpret_cast<const half8_t*>(af_smem + wa_ + tn * 2048);    \
+    _Pragma("unroll") for (int tm = 0; tm < TM; ++tm) xf[tm] = *reinterpret_cast<const half8_t*>(af_smem + fa[T][tm]);          \
+    _Pragma("unroll") for (int tn = 0; tn < TN; ++tn) wf1[tn] = *reinterpret_cast<const half8_t*>(af_smem + wb_ + tn * 2048);   \
+    _Pragma("unroll") for (int tm = 0; tm < TM; ++tm) xf1[tm] = *reinterpret_cast<const half8_t*>(af_smem + (fa[T][tm] ^ 64));  \
+  }
+    // the weights of the stage A stages ahead of stage T of chunk u (A = 1: group 0, A = 2: group 1), and this wave's halo pieces 2 T and 2 T + 1 of chunk u + 1
+#define CHU_ISSUE(T, A)                                                                                                          \
+  {                                                                                                                              \
+    if (!(first && (T) + (A) == 1) && !(last && (T) + (A) >= 4))                                                                 \
+      issue_wo((((T) + (A)) & 3) * Cin + ((T) + (A) < 4 ? u : u + 1) * 64, CHU_SLOT((T) + (A)));                                 \
+    if (!last && (T) < 3) {                                                                                                      \
+      issue_halo_piece(2 * ((T) % 3), hsrc, hld2, nbuf);                                                                         \
+      issue_halo_piece(2 * ((T) % 3) + 1, hsrc, hld2, nbuf);                                                                     \
+    }                                                                                                                            \
+  }
+#define CHU_NEXT_CHUNK                                                                                                           \
+  {                                                                                                                              \
+    const int d = ((u - cb) & 1) ? -CH_ASZ : CH_ASZ;                 /* the next chunk's halo lies in the other buffer */       \
+    _Pragma("unroll") for (int tap = 0; tap < 4; ++tap) _Pragma("unroll") for (int tm = 0; tm < TM; ++tm) fa[tap][tm] += d;     \
+    const int w_ = ws0;                                                                                                          \
+    ws0 = ws1, ws1 = ws2, ws2 = w_;                                                                                              \
+  }
+    if (grp == 0) {
+#pragma nounroll
+      for (int u = cb; u < ce; ++u) {
+        const bool first = u == cb, last = u + 1 == ce;
+        const half_t* hsrc = a1r;
+        int hld2 = 0;
+        if (!last) chunk_src(u + 1, hsrc, hld2);
+        const int nbuf = ((u + 1 - cb) & 1) * CH_ASZ;
+#define CHU_STAGE0(T)                                                                                                            \
+        {                                                                                                                        \
+          CHU_READ_FRAGS(T)                                                                                                      \
+          CHU_ISSUE(T, 1)                                                                                                        \
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                     \
+          __builtin_amdgcn_sched_barrier(0);                                                                                     \
+          __builtin_amdgcn_s_barrier();                                                                                          \
+          __builtin_amdgcn_sched_barrier(0);                                                                                     \
+          __builtin_amdgcn_s_setprio(0);                                                                                         \
+          mfmas();                                                                                                               \
+          __builtin_amdgcn_s_setprio(1);                                                                                         \
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                       \
+          __builtin_amdgcn_sched_barrier(0);                                                                                     \
+          __builtin_amdgcn_s_barrier();                                                                                          \
+          __builtin_amdgcn_sched_barrier(0);                                                                                     \
+        }
+        CHU_STAGE0(0) CHU_STAGE0(1) CHU_STAGE0(2) CHU_STAGE0(3)
+#undef CHU_STAGE0
+        CHU_NEXT_CHUNK
+      }
+      __builtin_amdgcn_s_barrier();                                  // group 1's last interval
+    } else {
+#pragma nounroll
+      for (int u = cb; u < ce; ++u) {
+        const bool first = u == cb, last = u + 1 == ce;
+        const half_t* hsrc = a1r;
+        int hld2 = 0;
+        if (!last) chunk_src(u + 1, hsrc, hld2);
+        const int nbuf = ((u + 1 - cb) & 1) * CH_ASZ;
+#define CHU_STAGE1(T)                                                                                                            \
+        {                                                                                                                        \
+          if (!(first && (T) == 0)) {                                                                                            \
+            __builtin_amdgcn_s_setprio(0);                                                                                       \
+            mfmas();                                                                                                             \
+            __builtin_amdgcn_s_setprio(1);                                                                                       \
+          }                                                                                                                      \
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                       \
+          __builtin_amdgcn_sched_barrier(0);                                                                                     \
+          __builtin_amdgcn_s_barrier();                                                                                          \
+          __builtin_amdgcn_sched_barrier(0);                                                                                     \
+          CHU_READ_FRAGS(T)                                                                                                      \
+          CHU_ISSUE(T, 2)                                                                                                        \
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                     \
+          __builtin_amdgcn_sched_barrier(0);                                                                                     \
+          __builtin_amdgcn_s_barrier();                                                                                          \
+          __builtin_amdgcn_sched_barrier(0);                                                                                     \
+        }
+        CHU_STAGE1(0) CHU_STAGE1(1) CHU_STAGE1(2) CHU_STAGE1(3)
+#undef CHU_STAGE1
+        CHU_NEXT_CHUNK
+      }
+      if (nchunks > 0) {                                             // M(last stage)
+        __builtin_amdgcn_s_setprio(0);
+        mfmas();
+        __builtin_amdgcn_s_setprio(1);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
+#undef CHU_NEXT_CHUNK
+#undef CHU_ISSUE
+#undef CHU_READ_FRAGS
+#undef CHU_SLOT
+  } else if (grp == 0) {
 #pragma nounroll
     for (int u = cb; u < ce; ++u) {
       const bool first = u == cb, last = u + 1 == ce;
@@ -1778,15 +1916,33 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
     __builtin_amdgcn_s_barrier();                                    // the staged epilogue reuses the LDS
   }
   __builtin_amdgcn_s_setprio(0);
-  gemm3_epilogue<E3_STD, NWM, NWN, TN, CH_LDS, PATCH>(p, acc, af_smem, tile_m, tile_n, wm, wn, fr, fq, tid);
+  gemm3_epilogue<E3_STD, NWM, NWN, TN, CH_LDS, UP2 ? 2 : (PATCH ? 1 : 0)>(p, acc, af_smem, tile_m, tile_n, wm, wn, fr, fq, tid);
 }
 
 // scope of the halo-resident kernel, stated here only: af_gemm3_try_launch launches on it and ops.conv_halo_eligible asks it through af_gemm_halo_variant.
 // It reads shape and mode fields, no operand pointer, so a host-side descriptor gets the answer of a launch (af_gemm has refused a K tail without a3 / a4
 // before it gets here).
 // 0 = outside; 1 = the 256 x 160 tile on whole image rows (the U-Net's levels); 2 = the 256 x 128 tile on whole image rows; 3 = the 256 x 128 tile on
-// 16 x 16-pixel patches (images wider than 64 pixels: the VAE decoder's 128 / 256 / 512 levels)
+// 16 x 16-pixel patches (images wider than 64 pixels: the VAE decoder's 128 / 256 / 512 levels); 4 = the phase form of the nearest-x2 convolution
+// (upsample = 3): the 256 x 160 tile on whole rows of the LOW-res image, four stages per chunk
+//
+// The phase form's scope: one source, 64-multiples of input channels, Cout % 160 == 0 (an N tile lies in one phase), W in {16, 32} and whole 256-pixel tiles
+// per image (halo 18 x 18 = 324 or 10 x 34 = 340 pixels: at most 43 pieces, the six per wave its loop issues), no split-K, nothing in the epilogue but the bias
+// (and an activation).  Not the 8 x 8 level (it needs split-K with a phase-mapped reduce), not the patch form, not 128-multiples of channels.
+static bool conv3h_up2_ok(const af_gemm_desc* d) {
+  if (d->taps != 9 || d->tap_shift || (d->stride ? d->stride : 1) != 1 || d->c1 <= 0 || d->c1 % 64 != 0 || d->c2 || d->c3 || d->c4) return false;
+  if (d->N <= 0 || d->N % CH_BN != 0 || d->K != 4 * d->c1 || d->kpad % 64 != 0 || d->kpad < d->K) return false;
+  if ((d->W != 16 && d->W != 32) || d->H <= 0 || d->B <= 0 || (d->H * d->W) % CH_BM != 0 || d->Ho != 2 * d->H || d->Wo != 2 * d->W) return false;
+  if ((long)d->M != (long)d->B * d->Ho * d->Wo || d->splits > 1) return false;
+  if (d->act == AF_ACT_GEGLU || d->out_mode != AF_OUT_NORMAL || d->ln_colsum != nullptr) return false;
+  if (d->rowbias != nullptr || d->residual != nullptr || d->gn_partials != nullptr) return false;
+  if ((long)d->B * d->H * d->W * d->c1 * 2 >= (1L << 32)) return false;                       // the halo gather's 32-bit byte offsets
+  if ((long)((4L * d->N + 127) / 128 * 128) * d->kpad * 2 >= (1L << 32)) return false;        // ... and the weight pieces' (w_off), on the 4 Cout x 4 Cin pack
+  return true;
+}
+
 static int conv3h_variant(const af_gemm_desc* d) {
+  if (d->upsample == 3) return conv3h_up2_ok(d) ? 4 : 0;
   if (d->taps != 9 || (d->upsample != 0 && d->upsample != 1) || d->tap_shift || d->c1 % 64 != 0 || d->c2 % 64 != 0) return 0;
   const bool n160 = d->N % CH_BN == 0;
   if (!n160 && d->N % 128 != 0) return 0;
@@ -1816,8 +1972,8 @@ static int conv3h_chunks(const af_gemm_desc* d) { return (d->c1 + d->c2) / 64; }
 
 static bool launch_conv3h(const Gemm3Dev& p0, hipStream_t stream, bool r5_loop, int variant) {
   Gemm3Dev p = p0;
-  p.tiles_n = p.N / (variant == 1 ? CH_BN : 128);
-  p.tiles_m = p.M / CH_BM;
+  p.tiles_n = p.N / ((variant == 1 || variant == 4) ? CH_BN : 128);
+  p.tiles_m = (variant == 4 ? p.M / 4 : p.M) / CH_BM;             // (the phase form's tiles are 256 LOW-res pixels)
   p.patch_tx = p.Wo / 16;
   p.patch_tpi = p.patch_tx * (p.Ho / 16);
   {
@@ -1828,6 +1984,12 @@ static bool launch_conv3h(const Gemm3Dev& p0, hipStream_t stream, bool r5_loop, 
   if (p.counters && (p.splits <= 1 || p.splits > 4 || p.tiles_m * p.tiles_n > AF_SPLITK_MAX_TILES)) p.counters = nullptr;
   p.n_major = af_gemm_n_major(p.M, p.N, p.K, p.c1 + p.c2);
   dim3 grid(p.tiles_m * p.tiles_n, p.splits), block(512);
+  if (variant == 4) {                                              // the phase form of the nearest-x2 convolution
+    static bool set_4 = false;
+    if (af_allow_dyn_lds(reinterpret_cast<const void*>(&af_conv3hd_kernel<false, 5, false, true>), CH_LDS, set_4, "af_gemm"))
+      hipLaunchKernelGGL((af_conv3hd_kernel<false, 5, false, true>), grid, block, CH_LDS, stream, p);
+    return false;
+  }
   if (variant >= 2) {                                              // 256 x 128 tile (round 6): the diet loop only
     static bool set_2 = false, set_3 = false;
     if (variant == 2) {
@@ -2190,7 +2352,8 @@ int af_gemm3_try_launch(const af_gemm_desc* d, int splits, int wide, hipStream_t
   const int halo_variant = wide == 11 ? conv3h_variant(d) : 0;
   if (wide == 11 && halo_variant == 0) return 1;                // halo-resident 3x3 kernel (tile 14)
   if (halo_r5 && (d->c3 > 0 || halo_variant != 1)) return 1;    // (the K tail and the 256 x 128 forms exist in the round-6 loop only)
-  if (d->upsample && !((wide == 4 || wide == 5 || (wide >= 8 && wide <= 12)) && d->upsample == 1 && d->taps == 9)) return 1;   // nearest x2: whole-line kernel only
+  if (d->upsample == 3 && halo_variant != 4) return 1;          // the phase form: tile 14 inside conv3h_up2_ok, nothing else
+  if (d->upsample && d->upsample != 3 && !((wide == 4 || wide == 5 || (wide >= 8 && wide <= 12)) && d->upsample == 1 && d->taps == 9)) return 1;   // nearest x2: whole-line kernel only
   if (d->c1 % BK3 != 0 || d->c2 % BK3 != 0 || d->zeros == nullptr) return 1;
   if (d->c3 > 0 && (wide < 4 || (wide > 10 && wide != 12 && wide != 11) || d->taps != 9 || d->upsample || (d->stride != 0 && d->stride != 1))) return 1;   // K tail: whole-line tap-by-tap tiles + the halo-resident kernel
   if ((geglu || split_t) && (d->taps != 1 || splits > 1)) return 1;
@@ -2214,6 +2377,7 @@ int af_gemm3_try_launch(const af_gemm_desc* d, int splits, int wide, hipStream_t
   if (d->ln_colsum != nullptr && (wide < 4 || d->taps != 1 || d->c2 != 0 || splits > 1)) return 1;   // folded LayerNorm: whole-line tiles only
   if (d->gn_partials != nullptr && !((wide == 4 || wide == 8 || wide == 10 || wide == 11) && !geglu && !split_t && splits <= 1)) return 1;   // GroupNorm partials: staged standard epilogue
   Gemm3Dev p;
+  p.up2_cout = 0;
   bool fused = false;
   p.ln_cs = (const float*)d->ln_colsum;
   p.ln_eps = d->ln_eps;
@@ -2292,6 +2456,17 @@ int af_gemm3_try_launch(const af_gemm_desc* d, int splits, int wide, hipStream_t
     if (halo_variant == 3) {
       if (!p.stage_ok) return 1;                                 // (the patch form leaves through the staged epilogue only)
       p.splits = 1;
+    }
+    if (halo_variant == 4) {                                     // the kernel sees a stride-1 convolution of the low-res image with 4 Cout phase-major rows
+      if (!p.stage_ok || splits > 1) return 1;
+      p.up2_cout = d->N;
+      p.N = 4 * d->N;
+      p.npad = (p.N + 127) / 128 * 128;
+      p.Ho = d->H;
+      p.Wo = d->W;
+      p.HoWo = d->H * d->W;
+      p.upsample = 0;
+      p.counters = nullptr;
     }
     fused = launch_conv3h(p, stream, halo_r5, halo_variant);
     return (p.splits > 1 && !fused) ? 2 : 0;

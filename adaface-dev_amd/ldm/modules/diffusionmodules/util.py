@@ -13,6 +13,8 @@ Same public names and argument meaning (``timestep_embedding``, ``normalization`
   (``packed()``), and re-packed automatically when a parameter is modified or moved.
 """
 
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -96,9 +98,23 @@ class Conv2d(nn.Conv2d):
 
         return self._cache.get((self.weight, self.bias), build)
 
+    def packed_up2(self) -> ops.PackedWeight:
+        """The phase pack for nearest x2 + this convolution (ops.pack_conv3x3_up2), cached like packed()."""
+        _require_cuda(self.weight, "Conv2d")
+        if not hasattr(self, "_cache_up2"):
+            self._cache_up2 = _PackCache()
+        return self._cache_up2.get((self.weight, self.bias), lambda: ops.pack_conv3x3_up2(self.weight, self.bias, self.weight.device))
+
     def hip(self, x, x2=None, upsample=False, rowbias=None, residual=None, gn_groups=0):
         """x [B,H,W,C1] (+x2 [B,H,W,C2]) fp16 -> [B,Ho,Wo,Cout] fp16.  gn_groups > 0: the output feeds a GroupNorm of that many groups -- where
         the launch can, it leaves the partial statistics with the tensor (ops.GnPartials) and the GroupNorm skips its statistics pass."""
+        if upsample is True and self.kernel_size == (3, 3) and self.stride[0] == 1 and not gn_groups and os.environ.get("AF_UP2_PHASE", "1") != "0":
+            # nearest x2 + 3x3 as four 2x2 phase convolutions where the library's kernel covers the shape (the U-Net's 16 -> 32 and 32 -> 64 levels);
+            # AF_UP2_PHASE=0 (A/B switch, read per call): the nine-tap gather everywhere
+            B, H, W, c1 = x.shape
+            d = ops.conv_up2_desc(B, H, W, c1, self.out_channels, c2=0 if x2 is None else x2.shape[-1], rowbias=rowbias, residual=residual)
+            if ops.conv_up2_eligible(d):
+                return ops.conv3x3_up2(x, self.packed_up2(), tile=14, splits=1)
         pw = self.packed()
         cpg = self.out_channels // gn_groups if gn_groups and self.out_channels % gn_groups == 0 else 0
         if self.kernel_size == (3, 3):

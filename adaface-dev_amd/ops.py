@@ -71,6 +71,7 @@ class PackedWeight:
     ln_eps: float = 0.0
     k_tail: int = 0   # pack_conv3x3_skip: plain K columns behind the nine tap blocks (the ResBlock's 1x1 shortcut inside its second convolution)
     aliased: bool = False   # wt IS the caller's tensor (pack_matrix fast path): read-only -- in-place refresh paths must replace, never copy_ into it
+    up2: bool = False       # pack_conv3x3_up2: rows [4 N] phase-major, K = 4 cin (conv3x3_up2 only)
 
 
 def pack_matrix(w2d: torch.Tensor, bias: Optional[torch.Tensor], device, taps: int = 1, cin: int = 0) -> PackedWeight:
@@ -136,6 +137,31 @@ def pack_conv3x3_skip(w3: torch.Tensor, b3: Optional[torch.Tensor], w1: torch.Te
             b = b + b1.detach().float().to(b.device)
     pw = pack_matrix(w, b, device, taps=9, cin=cin)
     pw.k_tail = cs
+    return pw
+
+
+def up2_phase_weights(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> [4, Cout, 2, 2, Cin] in w's dtype: nearest x2 followed by the 3x3 convolution is, for the output pixels of parity (py, px),
+    a 2x2 convolution of the LOW-res image over the offsets {py - 1, py} x {px - 1, px} (tap i of output row 2y + py reads source row
+    y + floor((py + i - 1) / 2)).  Its weights are the sums of the 3x3 weights that fold onto one source pixel:
+        py = 0: a = 0 <- w0,       a = 1 <- w1 + w2          py = 1: a = 0 <- w0 + w1,  a = 1 <- w2          (the same in x)
+    phase = 2 py + px.  Pass fp32 (or fp64) weights: the sums are meant to be rounded to fp16 ONCE, afterwards."""
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    fold = w.new_zeros((2, 2, 3))                                 # fold[parity, a, tap] = 1 where the tap lands on offset a
+    fold[0, 0, 0] = fold[0, 1, 1] = fold[0, 1, 2] = 1
+    fold[1, 0, 0] = fold[1, 0, 1] = fold[1, 1, 2] = 1
+    return torch.einsum("pai,qbj,ocij->pqoabc", fold, fold, w).reshape(4, cout, 2, 2, cin)
+
+
+def pack_conv3x3_up2(w: torch.Tensor, bias: Optional[torch.Tensor], device) -> PackedWeight:
+    """The phase pack of a 3x3 convolution that runs behind a nearest-x2 upsample (af_gemm_desc.upsample = 3): [4 Cout, 4 Cin], rows phase-major,
+    K order (a, b, cin); the sums formed in fp32 from the parameter and rounded to fp16 once (summing the rounded fp16 weights is 1.4x further
+    from fp64).  The bias stays the original [Cout]."""
+    cout, cin = w.shape[:2]
+    wp = up2_phase_weights(w.detach().to(device=device, dtype=torch.float32)).reshape(4 * cout, 4 * cin)
+    pw = pack_matrix(wp, bias, device, taps=9, cin=cin)
+    pw.N, pw.up2 = cout, True
     return pw
 
 
@@ -388,7 +414,7 @@ def _launch_gemm(d: "GemmDesc", device, what: str, tile: int = 0, splits: int = 
             gn = GnPartials.alloc(device, d.M // rpb, rpb, d.N, gn_cpg)
             d.gn_partials, d.gn_cpg = gn.ws.data_ptr(), gn_cpg
     if _weight_prefetcher is not None and _weight_prefetcher.mode is not None:
-        _weight_prefetcher.note(int(d.wt), int(d.kpad) * round_up(int(d.N), 128) * 2)
+        _weight_prefetcher.note(int(d.wt), int(d.kpad) * round_up(int(d.N) * (4 if d.upsample == 3 else 1), 128) * 2)
     _lib.check(_lib.lib().af_gemm(C.byref(d), _stream()), what)
     return gn
 
@@ -512,6 +538,40 @@ def conv3x3(x: torch.Tensor, pw: PackedWeight, *, x2: Optional[torch.Tensor] = N
     gn = _launch_gemm(d, x.device, "af_gemm(conv3x3)", tile, splits, gn_cpg=gn_cpg)
     if gn is not None:
         gn.attach(out)
+    return out
+
+
+def conv_up2_desc(B: int, H: int, W: int, c1: int, cout: int, *, c2: int = 0, rowbias=None, residual=None, splits: int = 1) -> "GemmDesc":
+    """The descriptor of nearest x2 + 3x3 in its phase form (upsample = 3; K = 4 c1 on the pack_conv3x3_up2 weights), shape and mode fields and the
+    epilogue operands only -- what conv_up2_eligible reads."""
+    d = GemmDesc()
+    d.rowbias, d.residual = _p(rowbias), _p(residual)
+    d.M, d.N, d.K, d.kpad, d.taps = B * 4 * H * W, cout, 4 * c1, round_up(4 * c1, 64), 9
+    d.c1, d.c2 = c1, c2
+    d.B, d.H, d.W, d.Ho, d.Wo = B, H, W, 2 * H, 2 * W
+    d.stride, d.upsample = 1, 3
+    d.rows_per_batch = 4 * H * W
+    d.ld_rowbias = 0 if rowbias is None else rowbias.stride(0)
+    d.splits = splits
+    return d
+
+
+def conv_up2_eligible(d) -> bool:
+    """Whether af_gemm runs the phase-form descriptor ``d`` (conv_up2_desc) -- the library's own launch predicate, as conv_halo_eligible."""
+    return _lib.lib().af_gemm_halo_variant(C.byref(d)) == 4
+
+
+def conv3x3_up2(x: torch.Tensor, pw: PackedWeight, *, tile: int = 14, splits: int = 1) -> torch.Tensor:
+    """Nearest x2 + 3x3 / pad 1 as four 2x2 phase convolutions of x [B,H,W,Cin] -> [B,2H,2W,Cout] (pw from pack_conv3x3_up2).  Runs on the
+    halo-resident kernel's phase form only: outside conv_up2_eligible the library refuses (callers ask first and keep conv3x3(upsample=True))."""
+    _chk_f16(x, "conv3x3_up2.x")
+    B, H, W, c1 = x.shape
+    assert pw.up2 and pw.cin == c1, f"conv3x3_up2: needs a pack_conv3x3_up2 weight of {c1} input channels"
+    out = torch.empty((B, 2 * H, 2 * W, pw.N), dtype=F16, device=x.device)
+    d = conv_up2_desc(B, H, W, c1, pw.N)
+    assert d.K == pw.K and d.kpad == pw.kpad
+    d.a1, d.wt, d.bias, d.out = _p(x), _p(pw.wt), _p(pw.bias), _p(out)
+    _launch_gemm(d, x.device, "af_gemm(conv3x3_up2)", tile, splits)
     return out
 
 

@@ -100,7 +100,11 @@ typedef struct af_gemm_desc {
   int32_t B, H, W;      /* taps==9 input image (before upsample) */
   int32_t Ho, Wo;       /* taps==9 output image */
   int32_t stride;       /* 1 | 2 */
-  int32_t upsample;     /* 0 | 1 (nearest x2) | 2 (zero-insert x2) */
+  int32_t upsample;     /* 0 | 1 (nearest x2) | 2 (zero-insert x2) | 3 (nearest x2 in PHASE form: the four output parities (py, px) as four 2x2
+                           convolutions of the low-res image.  wt = the phase pack [4 N][kpad], rows phase-major (phase = 2 py + px), K = 4 c1 in
+                           (a, b, cin) order, weight (a, b) of a phase = the sum of the 3x3 weights whose taps read low-res offset
+                           (py - 1 + a, px - 1 + b); bias stays [N]; H, W = the low-res image, Ho = 2 H, Wo = 2 W, M = B Ho Wo, taps = 9.
+                           Runs on tile 14 inside af_gemm_halo_variant's scope (answer 4) only; AF_E_UNSUPPORTED anywhere else) */
   int32_t rows_per_batch;
   int32_t ld_rowbias;
   int32_t act;
@@ -255,7 +259,9 @@ int af_groupnorm_apply(const void* x, int C, const void* gamma, const void* beta
 /* 1 when af_gemm with this (tile, splits) takes gn_partials for an output of N channels in groups of cpg and rows_per_batch rows per batch item */
 int af_gemm_gn_stats_ok(int tile, int splits, int taps, int act, int out_mode, int N, int cpg, int rows_per_batch);
 /* Which form of the halo-resident 3x3 kernel (tile 14) this descriptor would run: 0 = outside its scope (af_gemm falls back to a tap-by-tap tile),
- * 1 = 256 x 160 tiles on whole image rows, 2 = 256 x 128 tiles on whole image rows, 3 = 256 x 128 tiles on 16 x 16-pixel patches.  This is the
+ * 1 = 256 x 160 tiles on whole image rows, 2 = 256 x 128 tiles on whole image rows, 3 = 256 x 128 tiles on 16 x 16-pixel patches, 4 = the phase form
+ * of the nearest-x2 convolution (upsample = 3: one source, c1 % 64 == 0, N % 160 == 0, W in {16, 32}, H W % 256 == 0, no split-K, no rowbias /
+ * residual / gn_partials -- whether those three are set is read, nothing behind them).  This is the
  * predicate af_gemm itself launches on, and the only statement of that scope: callers ask it instead of repeating it.  Reads the shape and mode fields
  * only (taps, c1 .. c4, lda3, lda4, N, M, kpad, B, H, W, Ho, Wo, stride, upsample, tap_shift, act, out_mode, splits, and whether ln_colsum is set), no
  * operand pointer, so a host-side descriptor without operands gets the answer of the real launch; no launch. */
