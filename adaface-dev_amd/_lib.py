@@ -37,6 +37,7 @@ EXPORTS = (
     "af_cfg_ddim_inpaint_step", "af_cfg_dpmpp_inpaint_step", "af_cfg_lcm_inpaint_step", "af_vae_latents_z_q_sample",
     "af_vae_attention", "af_latent_resize_q_sample", "af_affine_prelu_ch", "af_face_align_crop",
     "af_stem_im2col7x7", "af_relu_maxpool3x3s2", "af_subsample2x", "af_upsample2x_add", "af_retina_decode", "af_retina_nms",
+    "af_face_alpha_mask", "af_crop_resize_u8", "af_paste_back_u8",
 )
 
 
@@ -187,6 +188,9 @@ def lib() -> C.CDLL:
     L.af_upsample2x_add.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.af_retina_decode.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, f32, vp, vp, i32, vp]
     L.af_retina_nms.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, vp]
+    L.af_face_alpha_mask.argtypes = [vp, vp, i32, i32, i32, f32, vp]
+    L.af_crop_resize_u8.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]
+    L.af_paste_back_u8.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     L.af_maxpool2x2.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.af_global_avgpool.argtypes = [vp, vp, i32, i32, i32, vp]
     L.af_se_residual_prelu.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]

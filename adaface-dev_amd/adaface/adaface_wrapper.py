@@ -54,8 +54,21 @@ resampled to the target size, ``hires_upscaler`` "bilinear" or "bicubic", and no
 nearest, pixel-space and model-based upscalers, hires for img2img / inpaint and graph capture of the two passes are not built.
 
 SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, U-Net ensembles and the
-ConsistentID encoder are out of scope (external packages).  Of inpainting, 9-channel inpainting U-Nets, ``padding_mask_crop`` /
-pixel paste-back, caller-supplied ``masked_image_latents``, graph capture of the loop and automatic face masks are not built."""
+``forward(photo, ..., mask_image="face", crop_padding=0.5)`` (``inpaint`` only; INTEGRATION.md "Repainting faces in a photo") repaints
+the faces of ONE photo of any size (a PIL image, a path or a uint8 array) and hands back the same photo: ``face_detector`` (any callable
+with ``FaceIDExtractor``'s detector contract, e.g. a ``RetinaFaceDetector``; by default the ``face_id_extractor``'s) finds the faces,
+``ops.face_alpha_mask`` draws a soft elliptical mask on the device (``face_mask_expand``, ``face_mask_feather``; ``face_index=k`` keeps
+the k-th face only), ``face_repaint.crop_region`` picks a padded rectangle around them, ``ops.crop_resize_u8`` resamples it to
+``work_size`` (default 512 x 512) and derives the latent mask, the inpaint machinery above runs unchanged, and ``ops.paste_back_u8``
+resamples the decoded crop back, blends it into the photo under the soft mask and quantises, in one launch.  Pixels that are not
+repainted come back bit-identical.  ``crop_padding=None`` with ``"face"`` runs the whole photo (through ``img2img_images_u8``'s size
+rules) and pastes back, so unmasked pixels are exact; a PIL mask with ``crop_padding`` runs the crop path under the hard mask v >= 128
+around the mask's bounding box; a PIL mask without ``crop_padding`` is the plain inpaint path above.  Still not built: one pass per
+face, Gaussian-blurred user masks, 9-channel inpainting U-Nets and graph capture of the loop.
+
+SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, U-Net ensembles and the
+ConsistentID encoder are out of scope (external packages).  Of inpainting, 9-channel inpainting U-Nets, caller-supplied
+``masked_image_latents`` and graph capture of the loop are not built."""
 import re
 import zlib
 
@@ -68,9 +81,11 @@ from ..ldm.models.diffusion.ddim import DDIMSampler
 from ..ldm.models.diffusion.ddpm import LatentDiffusion
 from ..ldm.models.diffusion.dpm_solver import DPMSolverSampler
 from ..ldm.models.diffusion.lcm import LCMSampler, lcm_timesteps
-from . import sd_lora
+from . import face_repaint, sd_lora
 from .arc2face_models import CLIPTextModelWrapper, clip_text_config
+from .face_align import load_rgb_u8
 from .face_id_to_ada_prompt import Arc2Face_ID2AdaPrompt
+from .face_repaint import FaceDetectorMissing, NoFaceFound      # noqa: F401  (re-exported: what forward(mask_image="face") raises)
 from .subj_basis_generator import CLIP_BOS, CLIP_EOS, CLIP_IDS
 
 
@@ -195,7 +210,7 @@ class AdaFaceWrapper(nn.Module):
                  num_inference_steps=50, subject_string="z", negative_prompt=None, max_prompt_length=77,
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
-                 lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None):
+                 lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None, face_detector=None):
         super().__init__()
         if pipeline_name not in ("text2img", "img2img", "inpaint", None):
             raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img, img2img and inpaint paths (and None = face "
@@ -244,6 +259,8 @@ class AdaFaceWrapper(nn.Module):
         if adaface_encoder_cfg_scales is not None:
             self.id2ada_prompt_encoder.out_id_embs_cfg_scale = adaface_encoder_cfg_scales[0]
         self.encoders_num_id_vecs = [self.id2ada_prompt_encoder.num_id_vecs]
+        # forward(mask_image="face"): any callable with FaceIDExtractor's detector contract; by default the extractor's own
+        self.face_detector = face_detector if face_detector is not None else getattr(face_id_extractor, "detect_faces", None)
         self.ldm = None if pipeline_name is None else (ldm or LatentDiffusion(unet_config or SD15_UNET_CONFIG))
         self.vae = vae
         self.img_prompt_embs = None
@@ -432,9 +449,11 @@ class AdaFaceWrapper(nn.Module):
                 out_image_count=4, ref_img_strength=0.8, generator=None, ablate_prompt_only_placeholders=False,
                 ablate_prompt_no_placeholders=False, ablate_prompt_embed_type="ada", nonmix_prompt_emb_weight=0,
                 repeat_prompt_for_each_encoder=True, verbose=False, mask_image=None, hires_size=None, hires_strength=0.7,
-                hires_steps=None, hires_upscaler="bilinear"):
+                hires_steps=None, hires_upscaler="bilinear", crop_padding=None, face_index=None, face_mask_expand=1.3,
+                face_mask_feather=0.25, work_size=None):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
+        repaint = self._check_repaint(noise, mask_image, crop_padding, face_index, face_mask_expand, face_mask_feather, work_size)
         if hires_size is not None:
             hires_hw, hires_steps = self._check_hires(hires_size, hires_strength, hires_steps, hires_upscaler)
         inpaint = self.pipeline_name == "inpaint"
@@ -446,11 +465,16 @@ class AdaFaceWrapper(nn.Module):
             if self.vae is None or not hasattr(self.vae, "encode_q_sample"):
                 raise ValueError(f"the {self.pipeline_name} pipeline encodes its input images: it needs an AutoencoderKL (encoder + "
                                  f"decoder) as vae, got {type(self.vae).__name__ if self.vae is not None else None}")
-            images_u8 = img2img_images_u8(noise, out_image_count)
-            if max(images_u8.shape[1:3]) > MAX_IMAGE_SIDE:
+            if repaint is not None:
+                self._sampler().img2img_steps(self.num_inference_steps, ref_img_strength)    # (before the detector runs)
+                repaint = self._repaint_plan(noise, mask_image, out_image_count, repaint)
+                images_u8 = None
+            else:
+                images_u8 = img2img_images_u8(noise, out_image_count)
+            if images_u8 is not None and max(images_u8.shape[1:3]) > MAX_IMAGE_SIDE:
                 raise ValueError(f"{self.pipeline_name} input images may be at most {MAX_IMAGE_SIDE} pixels on a side (the VAE's limit), got "
                                  f"{images_u8.shape[2]} x {images_u8.shape[1]}")
-            if inpaint:
+            if inpaint and repaint is None:
                 masks = inpaint_masks(mask_image, out_image_count, (images_u8.shape[2], images_u8.shape[1]))
             self._sampler().img2img_steps(self.num_inference_steps, ref_img_strength)    # refuse a bad strength before any work
         elif self.vae is not None and torch.is_tensor(noise) and noise.dim() == 4 and max(noise.shape[2:]) * 8 > MAX_IMAGE_SIDE:
@@ -482,11 +506,20 @@ class AdaFaceWrapper(nn.Module):
             return self._to_pil(latents)
         if inpaint:
             _, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
+            if repaint is not None:
+                photo = torch.from_numpy(repaint["photo"]).to(self.device)
+                if repaint["ellipses"] is not None:
+                    alpha = ops.face_alpha_mask(torch.from_numpy(repaint["ellipses"]).to(self.device), photo.shape[:2], repaint["feather"])
+                else:
+                    alpha = torch.from_numpy(repaint["hard_mask"]).to(self.device)
+                images_u8, masks = ops.crop_resize_u8(photo, alpha, repaint["rect"], repaint["work_hw"], 1.0 / 255.0)
             x_start, z, n_fwd = self.ldm.inpaint_latents(images_u8.to(self.device), out_image_count, t_first, generator=generator,
                                                          first_stage_model=self.vae, from_noise=ref_img_strength == 1)
             latents, _ = sampler.sample_inpaint(self.num_inference_steps, ref_img_strength, out_image_count, x_start, z, n_fwd,
                                                 masks.to(self.device), cond, guidance_scale=guidance_scale,
                                                 unconditional_conditioning=uncond, generator=generator)
+            if repaint is not None:
+                return self._paste_back(latents, photo, alpha, repaint["rect"])
             return self._to_pil(latents)
         noise = noise.to(device=self.device, dtype=torch.float32)
         latents, _ = sampler.sample(self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise,
@@ -519,14 +552,103 @@ class AdaFaceWrapper(nn.Module):
         self._sampler().img2img_steps(steps, hires_strength)        # a bad strength, or more steps than the sampler takes
         return (H // 8, W // 8), steps
 
+    def _check_repaint(self, photo, mask_image, crop_padding, face_index, face_mask_expand, face_mask_feather, work_size):
+        """The refusals of the photo-level inpaint path (INTEGRATION.md "Repainting faces in a photo"), all before any GPU work.  Returns
+        None for the plain paths (a PIL mask without crop_padding included), else the checked settings."""
+        face = isinstance(mask_image, str)
+        if face and mask_image != "face":
+            raise ValueError(f"mask_image as a string must be 'face', got {mask_image!r}")
+        if self.pipeline_name != "inpaint":
+            for name, v in (("crop_padding", crop_padding), ("face_index", face_index), ("work_size", work_size)):
+                if v is not None:
+                    raise ValueError(f"{name} is given but the pipeline is {self.pipeline_name!r}: only pipeline_name='inpaint' repaints a "
+                                     "region of a photo")
+            return None                             # (a mask_image on another pipeline is refused by forward itself)
+        if face and self.face_detector is None:
+            raise FaceDetectorMissing("mask_image='face' needs a face detector: pass face_detector (e.g. a RetinaFaceDetector) or a "
+                                      "face_id_extractor at construction")
+        if face_index is not None and not face:
+            raise ValueError("face_index selects among detected faces: it needs mask_image='face'")
+        if face_index is not None and (isinstance(face_index, bool) or not isinstance(face_index, (int, np.integer)) or face_index < 0):
+            raise ValueError(f"face_index must be a non-negative integer, got {face_index!r}")
+        if crop_padding is not None and not (isinstance(crop_padding, (int, float)) and 0 <= crop_padding < float("inf")):
+            raise ValueError(f"crop_padding must be a finite number >= 0 (or None), got {crop_padding!r}")
+        if not (isinstance(face_mask_expand, (int, float)) and 0 < face_mask_expand < float("inf")):
+            raise ValueError(f"face_mask_expand must be a finite positive number, got {face_mask_expand!r}")
+        if not (isinstance(face_mask_feather, (int, float)) and 0 <= face_mask_feather < float("inf")):
+            raise ValueError(f"face_mask_feather must be a finite number >= 0, got {face_mask_feather!r}")
+        if work_size is not None and crop_padding is None:
+            raise ValueError("work_size is the size the crop is resampled to: it needs crop_padding (without it the photo runs at its own size)")
+        work_hw = None
+        if crop_padding is not None:
+            work_hw = face_repaint.check_work_size((512, 512) if work_size is None else work_size, MAX_IMAGE_SIDE)
+        if not face and crop_padding is None:
+            return None
+        if isinstance(photo, (list, tuple)):
+            if len(photo) != 1:
+                raise ValueError(f"repainting a photo (mask_image='face' or crop_padding) takes one photo, got {len(photo)}")
+            photo = photo[0]
+        if not face and isinstance(mask_image, (list, tuple)):
+            if len(mask_image) != 1:
+                raise ValueError(f"crop_padding takes one mask image, got {len(mask_image)}")
+        return dict(face=face, crop_padding=crop_padding, face_index=face_index, expand=float(face_mask_expand),
+                    feather=float(face_mask_feather), work_hw=work_hw)
+
+    def _repaint_plan(self, photo, mask_image, out_image_count, cfg):
+        """Host preparation of the photo-level path: the photo's bytes, the ellipses (or the hard mask), the rectangle and the working
+        size.  The detector is the only GPU work in here."""
+        from PIL import Image
+        if isinstance(photo, (list, tuple)):
+            photo = photo[0]
+        rgb = load_rgb_u8(photo)
+        if cfg["crop_padding"] is None:             # the whole photo at its own size, under img2img's size rules
+            rgb = np.ascontiguousarray(img2img_images_u8(Image.fromarray(rgb), out_image_count)[0].numpy())
+            if max(rgb.shape[:2]) > MAX_IMAGE_SIDE:
+                raise ValueError(f"without crop_padding the whole photo is repainted: it may be at most {MAX_IMAGE_SIDE} pixels on a side "
+                                 f"(the VAE's limit), got {rgb.shape[1]} x {rgb.shape[0]}; pass crop_padding to repaint a region")
+        H, W = rgb.shape[:2]
+        if H * W * 3 >= 1 << 31:
+            raise ValueError(f"the photo needs 2^31 bytes or more ({W} x {H}): the kernels use 32-bit offsets")
+        plan = dict(photo=rgb, ellipses=None, hard_mask=None, feather=cfg["feather"])
+        if cfg["face"]:
+            plan["ellipses"] = face_repaint.face_ellipses(self.face_detector(rgb), cfg["face_index"], cfg["expand"])
+            boxes = face_repaint.ellipse_boxes(plan["ellipses"])
+        else:
+            m = mask_image[0] if isinstance(mask_image, (list, tuple)) else mask_image
+            if not isinstance(m, Image.Image):
+                raise ValueError(f"inpainting mask images must be PIL images (or the string 'face'), got {type(m).__name__}")
+            m = m.convert("L")
+            if m.size != (W, H):
+                m = m.resize((W, H), resample=Image.LANCZOS)
+            hard = np.asarray(m, dtype=np.uint8) >= 128
+            boxes = face_repaint.mask_bbox(hard)
+            plan["hard_mask"] = hard.astype(np.float32)
+        if cfg["crop_padding"] is None:
+            plan["rect"], plan["work_hw"] = (0, 0, W, H), (H, W)
+        else:
+            plan["work_hw"] = cfg["work_hw"]
+            plan["rect"] = face_repaint.crop_region(boxes, (H, W), cfg["work_hw"], cfg["crop_padding"])
+        return plan
+
+    def _paste_back(self, latents, photo, alpha, rect):
+        """Decode, then one ``ops.paste_back_u8`` launch and one device-to-host copy (per slice of photos that stays below 2^31 bytes)."""
+        from PIL import Image
+        decoded = self._decode(latents).float().contiguous()
+        per = max(1, (2 ** 31 - 1) // photo.numel())
+        out = [ops.paste_back_u8(decoded[i:i + per], photo, alpha, rect).cpu().numpy() for i in range(0, decoded.shape[0], per)]
+        return [Image.fromarray(im) for part in out for im in part]
+
     def _sampler(self):
         return LCMSampler(self.ldm) if self.use_lcm else SCHEDULERS[self.default_scheduler_name](self.ldm)
 
-    def _to_pil(self, latents):
+    def _decode(self, latents):
         # decode in slices of images that keep the widest activation (256 channels at full resolution) below 2^31 elements, the bound of the
         # kernels' 32-bit offsets: 8 images at 1024 x 1024, 32 at 512 x 512 -- one slice for every batch the pipelines run by default
         per = max(1, (2 ** 31 - 1) // (latents.shape[2] * latents.shape[3] * 64 * 256))
-        images = torch.cat([self.vae.decode(latents[i:i + per] / 0.18215) for i in range(0, latents.shape[0], per)])
+        return torch.cat([self.vae.decode(latents[i:i + per] / 0.18215) for i in range(0, latents.shape[0], per)])
+
+    def _to_pil(self, latents):
+        images = self._decode(latents)
         images = ((images.float() / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
         from PIL import Image
         return [Image.fromarray(im) for im in images]

@@ -1465,6 +1465,90 @@ def se_residual_prelu_bwd(x, se_logits, residual, slope, dy, dpool=None):
     return dx, dres
 
 
+# ----------------------------------------------------------------------------- repainting faces in a photo (af_repaint.hip)
+def _chk_photo(photo_u8, name):
+    if photo_u8.dtype != torch.uint8 or not photo_u8.is_cuda or not photo_u8.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous uint8 device tensor, got {photo_u8.dtype} {photo_u8.device} "
+                           f"contiguous={photo_u8.is_contiguous()}")
+    if photo_u8.dim() != 3 or photo_u8.shape[2] != 3 or photo_u8.numel() == 0:
+        raise RuntimeError(f"{name}: expected a non-empty [H, W, 3], got {tuple(photo_u8.shape)}")
+    if photo_u8.numel() >= 1 << 31:                          # (before any allocation: the C ABI refuses it too)
+        raise RuntimeError(f"{name}: {tuple(photo_u8.shape)} needs 2^31 bytes or more")
+
+
+def _chk_alpha(alpha, photo_u8, name):
+    H, W, _ = photo_u8.shape
+    if (alpha.dtype != torch.float32 or alpha.device != photo_u8.device or not alpha.is_contiguous() or tuple(alpha.shape) != (H, W)):
+        raise RuntimeError(f"{name}: expected contiguous fp32 [{H}, {W}] on {photo_u8.device}, got {alpha.dtype} {tuple(alpha.shape)} on "
+                           f"{alpha.device}")
+
+
+def _chk_rect(rect, H, W, name):
+    x0, y0, cw, ch = (int(v) for v in rect)
+    if x0 < 0 or y0 < 0 or cw < 1 or ch < 1 or x0 + cw > W or y0 + ch > H:
+        raise RuntimeError(f"{name}: the rectangle (x0, y0, cw, ch) = {(x0, y0, cw, ch)} must be non-empty and inside the {W} x {H} photo")
+    return x0, y0, cw, ch
+
+
+def face_alpha_mask(ellipses, photo_hw, feather):
+    """Ellipses fp32 [F, 4] rows (cx, cy, rx, ry) in photo pixels (F may be 0) -> the soft face mask alpha fp32 [H, W] on the ellipses'
+    device: smoothstep of (1 - r) / feather per face, maximum over the faces (af_face_alpha_mask; the rule is in include/adaface_hip.h)."""
+    if (ellipses.dtype != torch.float32 or not ellipses.is_cuda or not ellipses.is_contiguous() or ellipses.dim() != 2
+            or ellipses.shape[1] != 4):
+        raise RuntimeError(f"face_alpha_mask.ellipses: expected contiguous fp32 [F, 4] on the device, got {ellipses.dtype} "
+                           f"{tuple(ellipses.shape)} on {ellipses.device}")
+    H, W = (int(v) for v in photo_hw)
+    feather = float(feather)
+    if H < 1 or W < 1 or H * W * 3 >= 1 << 31:               # (before the allocation: the C ABI refuses it too)
+        raise RuntimeError(f"face_alpha_mask: the photo must be non-empty and need fewer than 2^31 bytes, got {W} x {H}")
+    if not 0 <= feather < float("inf"):
+        raise RuntimeError(f"face_alpha_mask: feather must be finite and >= 0, got {feather}")
+    alpha = torch.empty((H, W), dtype=torch.float32, device=ellipses.device)
+    nf = ellipses.shape[0]
+    _lib.check(_lib.lib().af_face_alpha_mask(_p(ellipses) if nf else None, _p(alpha), nf, H, W, feather, _stream()), "af_face_alpha_mask")
+    return alpha
+
+
+def crop_resize_u8(photo_u8, alpha, rect, work_hw, thr=1.0 / 255.0):
+    """photo uint8 [H, W, 3] and alpha fp32 [H, W], rect = (x0, y0, cw, ch), work_hw = (Hs, Ws) multiples of 8 -> (image uint8
+    [1, Hs, Ws, 3], mask_lat fp32 {0, 1} [1, 1, Hs/8, Ws/8]): the rectangle resampled by torch's antialiased bilinear rule and rounded to
+    even, and the latent cells whose 8 x 8 block of the resampled alpha reaches thr.  One launch (af_crop_resize_u8)."""
+    _chk_photo(photo_u8, "crop_resize_u8.photo")
+    _chk_alpha(alpha, photo_u8, "crop_resize_u8.alpha")
+    H, W, _ = photo_u8.shape
+    x0, y0, cw, ch = _chk_rect(rect, H, W, "crop_resize_u8")
+    Hs, Ws = (int(v) for v in work_hw)
+    if Hs < 8 or Ws < 8 or Hs % 8 or Ws % 8 or Hs * Ws * 3 >= 1 << 31:
+        raise RuntimeError(f"crop_resize_u8: the working size must be positive multiples of 8 below 2^31 bytes, got {Ws} x {Hs}")
+    image = torch.empty((1, Hs, Ws, 3), dtype=torch.uint8, device=photo_u8.device)
+    mask_lat = torch.empty((1, 1, Hs // 8, Ws // 8), dtype=torch.float32, device=photo_u8.device)
+    _lib.check(_lib.lib().af_crop_resize_u8(_p(photo_u8), _p(alpha), _p(image), _p(mask_lat), H, W, x0, y0, cw, ch, Hs, Ws, float(thr),
+                                            _stream()), "af_crop_resize_u8")
+    return image, mask_lat
+
+
+def paste_back_u8(decoded, photo_u8, alpha, rect):
+    """decoded fp32 [B, 3, Hs, Ws] (what the VAE decodes, nominally in [-1, 1]) resampled to the rectangle, mapped to [0, 255], blended into
+    the photo under alpha and rounded to even -> uint8 [B, H, W, 3]; outside the rectangle and wherever alpha == 0 the photo's own bytes.
+    One launch (af_paste_back_u8)."""
+    _chk_photo(photo_u8, "paste_back_u8.photo")
+    _chk_alpha(alpha, photo_u8, "paste_back_u8.alpha")
+    if (decoded.dtype != torch.float32 or decoded.device != photo_u8.device or not decoded.is_contiguous() or decoded.dim() != 4
+            or decoded.shape[1] != 3 or decoded.numel() == 0):
+        raise RuntimeError(f"paste_back_u8.decoded: expected non-empty contiguous fp32 [B, 3, Hs, Ws] on {photo_u8.device}, got {decoded.dtype} "
+                           f"{tuple(decoded.shape)} on {decoded.device}")
+    H, W, _ = photo_u8.shape
+    x0, y0, cw, ch = _chk_rect(rect, H, W, "paste_back_u8")
+    B, _, Hs, Ws = decoded.shape
+    if B * H * W * 3 >= 1 << 31 or decoded.numel() >= 1 << 31:
+        raise RuntimeError(f"paste_back_u8: {B} photos of {W} x {H} (or decoded {tuple(decoded.shape)}) need 2^31 bytes / elements or more; "
+                           "split the batch")
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=photo_u8.device)
+    _lib.check(_lib.lib().af_paste_back_u8(_p(decoded), _p(photo_u8), _p(alpha), _p(out), B, Hs, Ws, H, W, x0, y0, cw, ch, _stream()),
+               "af_paste_back_u8")
+    return out
+
+
 # ----------------------------------------------------------------------------- profiling hook
 def prof_enable(on: bool):
     _lib.check(_lib.lib().af_prof_enable(int(on)), "af_prof_enable")

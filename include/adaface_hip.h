@@ -555,6 +555,31 @@ int af_retina_decode(const void* head0, const void* head1, const void* head2, co
  * 1 <= max_det <= C <= 1024.                                                                                                            */
 int af_retina_nms(const void* cand, const void* count, void* out, void* out_counts, int B, int C, int max_det, float nms_thr, void* stream);
 
+/* ---- repainting faces in a photo (adaface/face_repaint.py; AdaFaceWrapper's inpaint pipeline with mask_image="face" / crop_padding): the
+ * pixel-space steps around the VAE.  photo: uint8 RGB [H, W, 3]; alpha: fp32 [H, W]; rectangle (x0, y0, cw, ch) non-empty and inside the
+ * photo.  32-bit offsets: H * W * 3 >= 2^31 (and B * H * W * 3 >= 2^31) is refused.  Every argument check precedes any launch (AF_E_BADARG,
+ * the function named in af_last_error()).  Four pixels of a row per lane: 12-byte / 16-byte accesses when W % 4 == 0 and the bases are
+ * aligned, byte / dword accesses otherwise.
+ *
+ * The resampling rule R(n_in -> n_out), separable, is torch's F.interpolate(mode="bilinear", antialias=True, align_corners=False):
+ *   s = n_in / n_out, sup = max(s, 1), c = s (i + 0.5); taps k in [max(0, int(c - sup + 0.5)), min(n_in, int(c + sup + 0.5)));
+ *   weight max(0, 1 - |(k - c + 0.5) / sup|) / (its sum over the taps).  Tap ranges and un-normalised weights are exact integers over
+ *   2 max(n_in, n_out); each normalised weight is one fp32 division; sums run along x, then y, in fp32.  At s = 1 it is the identity.
+ *
+ * Soft face mask.  ellipses fp32 [F, 4] rows (cx, cy, rx, ry) in photo pixels (device memory; NULL allowed when F = 0):
+ *   r = sqrt(((x + 0.5 - cx) / rx)^2 + ((y + 0.5 - cy) / ry)^2), t = clamp((1 - r) / feather, 0, 1), a_f = t^2 (3 - 2 t)
+ *   (feather = 0: a_f = (r <= 1)); alpha[y, x] = max_f a_f, 0 for F = 0.                                                                  */
+int af_face_alpha_mask(const void* ellipses, void* alpha, int F, int H, int W, float feather, void* stream);
+/* One launch: image uint8 [1, Hs, Ws, 3] = rint(clamp(R(photo[y0:y0+ch, x0:x0+cw]), 0, 255)) (ties to even; taps never leave the rectangle)
+ * and mask_lat fp32 [1, 1, Hs/8, Ws/8] = (max over the 8 x 8 block of R(alpha[y0:y0+ch, x0:x0+cw]) >= thr).  Hs, Ws: positive multiples of 8. */
+int af_crop_resize_u8(const void* photo_u8, const void* alpha, void* image_u8, void* mask_lat, int H, int W, int x0, int y0, int cw, int ch,
+                      int Hs, int Ws, float thr, void* stream);
+/* One launch: out uint8 [B, H, W, 3].  Outside the rectangle (and wherever alpha == 0) out = photo.  Inside, with d = R(decoded[b, c]) from
+ * (Hs, Ws) to (ch, cw), decoded fp32 [B, 3, Hs, Ws] in [-1, 1] nominally: g = 255 clamp(d / 2 + 0.5, 0, 1),
+ * out = rint(alpha g + (1 - alpha) p), ties to even, in this order and unfused: alpha = 0 gives p and alpha = 1 gives rint(g) bit for bit. */
+int af_paste_back_u8(const void* decoded, const void* photo_u8, const void* alpha, void* out_u8, int B, int Hs, int Ws, int H, int W, int x0,
+                     int y0, int cw, int ch, void* stream);
+
 /* ---- trainable DoRA adapters on the U-Net's up_blocks.3 convolutions (adaface/diffusers_attn_lora_capture.py:541-591; peft
  * DoraConv2dLayer.forward: y = base(x) + (s - 1) * conv(xd, W) + s * scaling * B(A(xd)), xd = dropout(x)) ---------------------
  * out = y0 + u[c] * c2 + v[c] * lb   (fp16 [rows, C]; u = s - 1, v = s * scaling, fp32 [C]) */
