@@ -38,6 +38,7 @@ EXPORTS = (
     "af_vae_attention", "af_latent_resize_q_sample", "af_affine_prelu_ch", "af_face_align_crop",
     "af_stem_im2col7x7", "af_relu_maxpool3x3s2", "af_subsample2x", "af_upsample2x_add", "af_retina_decode", "af_retina_nms",
     "af_face_alpha_mask", "af_crop_resize_u8", "af_paste_back_u8",
+    "af_temporal_attention",
 )
 
 
@@ -165,6 +166,7 @@ def lib() -> C.CDLL:
     L.af_softmax_rows.argtypes = [vp, vp, i64, i32, vp]
     L.af_mask_pairs.argtypes = [vp, vp, i32, vp]
     L.af_vae_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.af_temporal_attention.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
     L.af_prefetch.argtypes = [vp, i64, vp]
     L.af_prefetch_ex.argtypes = [vp, i64, i32, vp]
     L.af_xattn_scores.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]

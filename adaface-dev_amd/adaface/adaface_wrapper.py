@@ -53,6 +53,13 @@ resampled to the target size, ``hires_upscaler`` "bilinear" or "bicubic", and no
 ``sample_img2img`` over ``hires_strength`` of ``hires_steps`` (default ``num_inference_steps``) at the target size.  Antialiased,
 nearest, pixel-space and model-based upscalers, hires for img2img / inpaint and graph capture of the two passes are not built.
 
+``forward(noise, prompt, out_image_count=V, num_frames=F)`` (``text2img`` only; INTEGRATION.md "Video (motion modules)") generates V
+clips of F frames with an AnimateDiff motion module (``motion_module_path`` / ``load_motion_module``, a local ``.ckpt`` / ``.pth`` file
+or its state dict; ``ldm/modules/motion_module.py``): ``noise`` is ``[V * F, 4, h, w]`` video-major, the prompt is repeated per frame,
+the module sits on the U-Net during the sampling call only, and V lists of F images come back (the latents without a ``vae``).
+``beta_schedule="sqrt_linear"`` gives the plain-linear betas AnimateDiff's configs use.  Training, MotionLoRA, SparseCtrl, sliding
+context windows, img2video, the diffusers MotionAdapter layout and GIF / MP4 writing are not built.
+
 SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, U-Net ensembles and the
 ``forward(photo, ..., mask_image="face", crop_padding=0.5)`` (``inpaint`` only; INTEGRATION.md "Repainting faces in a photo") repaints
 the faces of ONE photo of any size (a PIL image, a path or a uint8 array) and hands back the same photo: ``face_detector`` (any callable
@@ -210,7 +217,8 @@ class AdaFaceWrapper(nn.Module):
                  num_inference_steps=50, subject_string="z", negative_prompt=None, max_prompt_length=77,
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
-                 lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None, face_detector=None):
+                 lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None, face_detector=None, motion_module_path=None,
+                 beta_schedule="linear"):
         super().__init__()
         if pipeline_name not in ("text2img", "img2img", "inpaint", None):
             raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img, img2img and inpaint paths (and None = face "
@@ -261,7 +269,11 @@ class AdaFaceWrapper(nn.Module):
         self.encoders_num_id_vecs = [self.id2ada_prompt_encoder.num_id_vecs]
         # forward(mask_image="face"): any callable with FaceIDExtractor's detector contract; by default the extractor's own
         self.face_detector = face_detector if face_detector is not None else getattr(face_id_extractor, "detect_faces", None)
-        self.ldm = None if pipeline_name is None else (ldm or LatentDiffusion(unet_config or SD15_UNET_CONFIG))
+        if ldm is not None and beta_schedule != "linear":
+            raise ValueError("beta_schedule is given together with a ready ldm: build that LatentDiffusion with the schedule instead")
+        # beta_schedule: make_beta_schedule's names -- "linear" is SD's scaled-linear table, "sqrt_linear" the plain-linear betas of AnimateDiff's configs
+        self.ldm = None if pipeline_name is None else (ldm or LatentDiffusion(unet_config or SD15_UNET_CONFIG, beta_schedule=beta_schedule))
+        self.__dict__["motion_module"] = None     # a MotionModule (load_motion_module); not a submodule: it is on the U-Net only inside forward(num_frames=F)
         self.vae = vae
         self.img_prompt_embs = None
         self._lcm_lora = None                 # (read_unet_lora dict, scale) of the fused LoRA
@@ -273,6 +285,8 @@ class AdaFaceWrapper(nn.Module):
         self.extend_tokenizer_and_text_encoder()
         if adaface_ckpt_paths:
             self.load_subj_basis_generator(adaface_ckpt_paths)
+        if motion_module_path is not None:
+            self.load_motion_module(motion_module_path)
 
     # ------------------------------------------------------------------ checkpoints
     def load_base_model(self, base_model_path):
@@ -295,6 +309,37 @@ class AdaFaceWrapper(nn.Module):
         if self._lcm_lora is not None:
             self._lcm_saved = sd_lora.fuse_unet_lora(self.ldm.model, *self._lcm_lora)
         return missing, unexpected
+
+    def load_motion_module(self, path_or_state_dict):
+        """An AnimateDiff motion module (a local ``.ckpt`` / ``.pth`` file or its state dict; ldm/modules/motion_module.py) for
+        ``forward(..., num_frames=F)``.  Strict: a file that does not match raises ValueError.  Nothing is downloaded."""
+        from ..ldm.modules.motion_module import MotionModule
+        if self.ldm is None:
+            raise RuntimeError("pipeline_name=None builds the face encoder only: there is no U-Net to put a motion module on")
+        mm = MotionModule(path_or_state_dict)
+        self.ldm.model.diffusion_model.set_motion(mm, 1)        # refuses widths that do not match this U-Net
+        self.ldm.model.diffusion_model.set_motion(None)
+        self.__dict__["motion_module"] = mm
+        return mm
+
+    def unload_motion_module(self):
+        self.__dict__["motion_module"] = None
+        if self.ldm is not None:
+            self.ldm.model.diffusion_model.set_motion(None)
+
+    def _check_video(self, noise, num_frames, out_image_count, hires_size):
+        """The refusals of forward(num_frames=F) (INTEGRATION.md "Video (motion modules)"), all before any GPU work."""
+        if self.motion_module is None:
+            raise ValueError("num_frames is given but no motion module is loaded (motion_module_path / load_motion_module)")
+        if self.pipeline_name != "text2img":
+            raise ValueError(f"num_frames is given but the pipeline is {self.pipeline_name!r}: only pipeline_name='text2img' generates video")
+        if hires_size is not None:
+            raise ValueError("num_frames together with hires_size: two-pass high-resolution video is not built")
+        if isinstance(num_frames, bool) or not isinstance(num_frames, int) or not 1 <= num_frames <= self.motion_module.max_len:
+            raise ValueError(f"num_frames must be an integer from 1 to {self.motion_module.max_len} (the module's position table), got {num_frames!r}")
+        if not torch.is_tensor(noise) or noise.dim() != 4 or noise.shape[0] != out_image_count * num_frames:
+            raise ValueError(f"video noise must be [out_image_count * num_frames = {out_image_count * num_frames}, 4, h, w], video-major; got "
+                             f"{tuple(noise.shape) if torch.is_tensor(noise) else type(noise).__name__}")
 
     def fuse_lcm_lora(self, path_or_state_dict, scale=1.0):
         """Fuse an SD-1.5 U-Net LoRA (a .safetensors / .bin / .pt file or a state dict in the kohya, diffusers or peft layout;
@@ -450,9 +495,13 @@ class AdaFaceWrapper(nn.Module):
                 ablate_prompt_no_placeholders=False, ablate_prompt_embed_type="ada", nonmix_prompt_emb_weight=0,
                 repeat_prompt_for_each_encoder=True, verbose=False, mask_image=None, hires_size=None, hires_strength=0.7,
                 hires_steps=None, hires_upscaler="bilinear", crop_padding=None, face_index=None, face_mask_expand=1.3,
-                face_mask_feather=0.25, work_size=None):
+                face_mask_feather=0.25, work_size=None, num_frames=None):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
+        if num_frames is not None:
+            self._check_video(noise, num_frames, out_image_count, hires_size)
+            videos = out_image_count
+            out_image_count = videos * num_frames          # the batch is video-major: row v * F + f, the prompt repeated per frame
         repaint = self._check_repaint(noise, mask_image, crop_padding, face_index, face_mask_expand, face_mask_feather, work_size)
         if hires_size is not None:
             hires_hw, hires_steps = self._check_hires(hires_size, hires_strength, hires_steps, hires_upscaler)
@@ -522,8 +571,16 @@ class AdaFaceWrapper(nn.Module):
                 return self._paste_back(latents, photo, alpha, repaint["rect"])
             return self._to_pil(latents)
         noise = noise.to(device=self.device, dtype=torch.float32)
-        latents, _ = sampler.sample(self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise,
-                                    verbose=False, guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
+        unet = self.ldm.model.diffusion_model
+        if num_frames is not None:
+            self.motion_module.to(self.device)
+            unet.set_motion(self.motion_module, num_frames)           # around the sampling call only
+        try:
+            latents, _ = sampler.sample(self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise,
+                                        verbose=False, guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
+        finally:
+            if num_frames is not None:
+                unet.set_motion(None)
         if hires_size is not None:
             _, t_first = sampler.img2img_steps(hires_steps, hires_strength)
             x_t = self.ldm.hires_latents(latents, hires_hw, t_first, generator, hires_upscaler)
@@ -531,6 +588,9 @@ class AdaFaceWrapper(nn.Module):
                                                 unconditional_conditioning=uncond, generator=generator)
         if self.vae is None:
             return latents
+        if num_frames is not None:
+            frames = self._to_pil(latents)
+            return [frames[v * num_frames:(v + 1) * num_frames] for v in range(videos)]
         return self._to_pil(latents)
 
     def _check_hires(self, hires_size, hires_strength, hires_steps, hires_upscaler):

@@ -396,6 +396,7 @@ class UNetModel(nn.Module):
             off += ops.round_up(rb.out_channels, 8)
         self._emb_total = off
         self._emb_cache = _PackCache()
+        self.__dict__["_motion"] = None          # (MotionModule, num_frames) while set_motion holds one; not a submodule: the state dict stays SD-1.5's
 
     # ------------------------------------------------------------------ reference flag plumbing
     ALL_CA_LAYER_INDICES = [1, 2, 4, 5, 7, 8, 12, 16, 17, 18, 19, 20, 21, 22, 23, 24]  # openaimodel.py:721
@@ -472,6 +473,50 @@ class UNetModel(nn.Module):
         self._packed_emb_all()
         return self
 
+    # ------------------------------------------------------------------ video (ldm/modules/motion_module.py)
+    def set_motion(self, motion, num_frames=0):
+        """Run ``motion`` (a MotionModule) inside ``hip`` on batches of whole ``num_frames``-frame videos (row ``v * F + f``); ``None`` restores the
+        image walk exactly.  Refuses (ValueError) a module whose widths do not match this U-Net or a frame count outside 1 .. its max_len."""
+        if motion is None:
+            self.__dict__["_motion"] = None
+            return
+        F = int(num_frames)
+        if not 1 <= F <= motion.max_len:
+            raise ValueError(f"set_motion: num_frames must be in 1 .. {motion.max_len} (the module's position table), got {num_frames}")
+        if len(self.channel_mult) != 4 or self.num_res_blocks != 2:
+            raise ValueError("set_motion: motion modules are placed on the SD-1.5 topology (4 levels of 2 ResBlocks)")
+        for (where, n), tt in motion.placed():
+            block = self.middle_block if where == "middle" else (self.input_blocks if where == "input" else self.output_blocks)[n]
+            ch = block[0].out_channels
+            if tt.channels != ch:
+                raise ValueError(f"set_motion: the module's transformer at {where} block {n} has {tt.channels} channels, the U-Net {ch}")
+        self.__dict__["_motion"] = (motion, F)
+
+    def _refuse_motion(self, what):
+        if self._motion is not None:
+            raise NotImplementedError(f"{what} is not built for video: unset the motion module (set_motion(None)) first")
+
+    def _hip_block_motion(self, module, where, n, h, emb, context, img_mask):
+        """``module.hip`` with the temporal transformer placed at (where, n), if any: behind an input block, between the middle block's
+        SpatialTransformer and its second ResBlock, in front of an output block's Upsample."""
+        motion, F = self._motion
+        tt = motion.at(where, n)
+        if tt is None:
+            return module.hip(h, emb, context, img_mask)
+        if h[0].shape[0] % F if isinstance(h, SkipCat) else h.shape[0] % F:
+            raise ValueError(f"the batch ({(h[0] if isinstance(h, SkipCat) else h).shape[0]}) is not a multiple of num_frames ({F})")
+        done = False
+        for k, layer in enumerate(module):
+            if not done and (isinstance(layer, Upsample) or (where == "middle" and k == 2)):
+                h, done = tt.hip(h, F), True
+            if isinstance(layer, TimestepBlock):
+                h = layer.hip(h, emb)
+            elif isinstance(layer, SpatialTransformer):
+                h = layer.hip(h, context, img_mask)
+            else:
+                h = layer.hip(h)
+        return h if done else tt.hip(h, F)
+
     # ------------------------------------------------------------------ forward
     def hip(self, x_nhwc, timesteps, context, img_mask=None, capture_layers=()):
         """x_nhwc [B,H,W,8] fp16 (4 latent channels + zero pad), timesteps int64 [B],
@@ -528,18 +573,28 @@ class UNetModel(nn.Module):
             acts[layer_idx] = a
             attn2.cached_activations = None
 
-        for module in self.input_blocks:
-            h = module.hip(h, emb, context, img_mask)
+        if self._motion is None:
+            def run(module, where, n, h):
+                return module.hip(h, emb, context, img_mask)
+        else:
+            if capture_layers:
+                raise NotImplementedError("capturing cross-attention activations is not built for video")
+
+            def run(module, where, n, h):
+                return self._hip_block_motion(module, where, n, h, emb, context, img_mask)
+
+        for n, module in enumerate(self.input_blocks):
+            h = run(module, "input", n, h)
             hs.append(h)
             if layer_idx in capture_layers:
                 collect(module, h)
             layer_idx += 1
-        h = self.middle_block.hip(h, emb, context, img_mask)
+        h = run(self.middle_block, "middle", 1, h)
         if layer_idx in capture_layers:
             collect(self.middle_block, h)
         layer_idx += 1
-        for module in self.output_blocks:
-            h = module.hip(SkipCat((h, hs.pop())), emb, context, img_mask)
+        for n, module in enumerate(self.output_blocks):
+            h = run(module, "output", n, SkipCat((h, hs.pop())))
             if layer_idx in capture_layers:
                 collect(module, h)
             layer_idx += 1
@@ -550,6 +605,7 @@ class UNetModel(nn.Module):
         """The inference walk of the last ``n_tail`` decoder blocks + the output head on trunk = (h, skips) as ``hip_trunk`` returns them
         (a step's shared gradient-free trunk, LatentDiffusion.guided_denoise): -> (eps NHWC, captured activations) exactly as ``_hip_blocks``
         leaves them for those layers."""
+        self._refuse_motion("the trunk cache (hip_tail)")
         h, skips = trunk
         emb = self._embed(timesteps)
         kv_layers = self._project_context_all(context)
@@ -580,6 +636,7 @@ class UNetModel(nn.Module):
 
     def hip_train(self, x_nhwc, timesteps, context, img_mask=None):
         """Forward that keeps the activations the backward needs.  -> (eps [B,H,W,out_channels], saved)."""
+        self._refuse_motion("hip_train")
         emb = self._embed(timesteps)
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
@@ -597,6 +654,7 @@ class UNetModel(nn.Module):
     def hip_train_trunk(self, x_nhwc, emb, context, img_mask, n_tail):
         """hip_train without the last ``n_tail`` decoder blocks and the output head (modules/diffusionmodules/capture_graph.py):
         -> (h, [the skips those blocks will pop, in pop order], saved)."""
+        self._refuse_motion("hip_train_trunk")
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
         for module in self.input_blocks:
@@ -615,6 +673,7 @@ class UNetModel(nn.Module):
         """``hip_train_trunk`` for a pass that needs NO gradient below the tail (a no-grad instance of a compositional step, or one whose
         input and context carry none): the inference walk -- every cross-attention layer's k / v from one GEMM, the fused C = 320 blocks,
         nothing saved -- up to the last ``n_tail`` decoder blocks.  -> (h, [the skips those blocks pop, in pop order])."""
+        self._refuse_motion("the trunk cache (hip_trunk)")
         kv_layers = self._project_context_all(context)
         try:
             hs = []
@@ -698,6 +757,7 @@ class UNetModel(nn.Module):
             # Stage-2 pass: explicit attention in the last three cross-attention layers (score rewrites, captures with gradients,
             # attention LoRAs) as a chain of autograd nodes -- modules/diffusionmodules/capture_graph.py
             from .capture_graph import unet_forward_captured
+            self._refuse_motion("the captured / score-rewrite path")
             if extra_info is None:
                 raise ValueError("extra_info must be a dict on the capture / score-rewrite path")
             if capture:
@@ -707,6 +767,7 @@ class UNetModel(nn.Module):
                 extra_info.pop("ca_layers_activations", None)
             return eps
         if trainable:
+            self._refuse_motion("training")
             gs = float((extra_info or {}).get("res_hidden_states_gradscale", 1) or 1)
             lora = (extra_info or {}).get("_ffn_lora_adapters")           # set by UNetWrapper when use_ffn_lora is on
             return _UNetFunction.apply(self, x, timesteps, context, img_mask, gs, lora, *[t[3] for t in lora_param_order(lora)])

@@ -1202,6 +1202,22 @@ def vae_attention(q, k, v, *, B: int, N: int, C: int):
     return o
 
 
+TEMPORAL_ATTN_MAX_FRAMES = 32      # af_temporal_attention: 1 <= F <= 32, head dim % 8 == 0 in 8 .. 160
+
+
+def temporal_attention(qkv, *, B: int, F: int, HW: int, heads: int, d: int, scale=None):
+    """Self-attention along the frame axis (motion modules): qkv [B*F*HW, >= 3*heads*d] fp16 token rows, row (b*F + f)*HW + p holding
+    q | k | v of frame f of pixel p -> [B*F*HW, heads*d], softmax over the F frames of each (b, p, head).  One launch, no workspace, no transpose."""
+    _chk_f16_rows(qkv, "temporal_attention.qkv")
+    Cn = heads * d
+    if qkv.shape[0] != B * F * HW or qkv.shape[1] < 3 * Cn:
+        raise RuntimeError(f"temporal_attention.qkv: expected [{B * F * HW}, >= {3 * Cn}], got {tuple(qkv.shape)}")
+    o = torch.empty((B * F * HW, Cn), dtype=F16, device=qkv.device)
+    rc = _lib.lib().af_temporal_attention(_p(qkv), _ld(qkv), _p(o), B, F, HW, heads, d, float(d ** -0.5 if scale is None else scale), _stream())
+    _lib.check(rc, "af_temporal_attention")
+    return o
+
+
 def softmax_rows_bwd(p, dp):
     """ds = p * (dp - rowsum(p * dp)) for fp16 [rows, L] probabilities and their gradient."""
     _chk_f16(p, "softmax_rows_bwd.p")

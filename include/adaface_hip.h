@@ -474,6 +474,14 @@ int af_softmax_rows(const void* x, void* y, int64_t rows, int L, void* stream);
  * reference / sum and fp32 accumulation; P is rounded to fp16 as the MFMA operand.  AF_E_UNSUPPORTED for another C and for an operand of 2^31
  * elements or more (offsets are not wrapped).                                                                                             */
 int af_vae_attention(const void* q, const void* k, const void* vt, void* o, int B, int N, int C, int ldq, int ldk, int ldv, int ldo, void* stream);
+/* Self-attention along the frame axis (AnimateDiff motion modules).  qkv fp16, row r = (b*F + f)*HW + p (batch item b, frame f, pixel p)
+ * holds q | k | v of that token at columns [0,C) | [C,2C) | [2C,3C), C = heads*d, row stride ld elements.
+ * out fp16 [B*F*HW][C]:  out[(b*F+f)*HW+p, h*d+j] = sum_g softmax_g(scale * <q_f, k_g>) * v_g[j], g over the F frames of the same (b, p, h).
+ * 1 <= F <= 32, d % 8 == 0, 8 <= d <= 160, ld % 8 == 0, ld >= 3C, 16-byte aligned pointers, any HW >= 1.  No workspace, one launch.
+ * fp32 scores, softmax and accumulation; P is rounded to fp16 as the MFMA operand.  Every qkv element is read once (16-byte loads), so a dense
+ * qkv costs 2 (3C + C) bytes per row.
+ * AF_E_BADARG (before any launch): NULL pointer, a size outside the above, B*F*HW*ld or B*F*HW*C >= 2^31. */
+int af_temporal_attention(const void* qkv, int ld, void* out, int B, int F, int HW, int heads, int d, float scale, void* stream);
 /* its backward, ds = p * (dp - rowsum(p * dp)), for the decode-with-grad path of the ArcFace alignment loss (ddpm.py:2511-2535
  * differentiates through decode_first_stage_with_grad, ddpm.py:899-908) */
 int af_softmax_rows_bwd(const void* p, const void* dp, void* ds, int64_t rows, int L, void* stream);
