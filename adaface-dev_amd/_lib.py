@@ -39,6 +39,7 @@ EXPORTS = (
     "af_stem_im2col7x7", "af_relu_maxpool3x3s2", "af_subsample2x", "af_upsample2x_add", "af_retina_decode", "af_retina_nms",
     "af_face_alpha_mask", "af_crop_resize_u8", "af_paste_back_u8",
     "af_temporal_attention",
+    "af_dense_conv3x3", "af_u8_unshuffle_f16",
 )
 
 
@@ -167,6 +168,8 @@ def lib() -> C.CDLL:
     L.af_mask_pairs.argtypes = [vp, vp, i32, vp]
     L.af_vae_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.af_temporal_attention.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
+    L.af_dense_conv3x3.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, f32, vp, i32, f32, f32, i32, i32, i32, i32, i32, vp]
+    L.af_u8_unshuffle_f16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     L.af_prefetch.argtypes = [vp, i64, vp]
     L.af_prefetch_ex.argtypes = [vp, i64, i32, vp]
     L.af_xattn_scores.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]

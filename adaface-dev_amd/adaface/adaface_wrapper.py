@@ -51,7 +51,8 @@ step but the last.  Nothing is downloaded: ``lcm_lora_path`` is a local file or 
 of the three samplers: the usual run at the size of ``noise``, then ``LatentDiffusion.hires_latents`` (one fused kernel: the latents
 resampled to the target size, ``hires_upscaler`` "bilinear" or "bicubic", and noised to the second pass's first timestep) and
 ``sample_img2img`` over ``hires_strength`` of ``hires_steps`` (default ``num_inference_steps``) at the target size.  Antialiased,
-nearest, pixel-space and model-based upscalers, hires for img2img / inpaint and graph capture of the two passes are not built.
+nearest and pixel-space upscalers between the passes, hires for img2img / inpaint and graph capture of the two passes are not built
+(model-based upscaling of the final images is ``upscale=True``, below).
 
 ``forward(noise, prompt, out_image_count=V, num_frames=F)`` (``text2img`` only; INTEGRATION.md "Video (motion modules)") generates V
 clips of F frames with an AnimateDiff motion module (``motion_module_path`` / ``load_motion_module``, a local ``.ckpt`` / ``.pth`` file
@@ -59,6 +60,12 @@ or its state dict; ``ldm/modules/motion_module.py``): ``noise`` is ``[V * F, 4, 
 the module sits on the U-Net during the sampling call only, and V lists of F images come back (the latents without a ``vae``).
 ``beta_schedule="sqrt_linear"`` gives the plain-linear betas AnimateDiff's configs use.  Training, MotionLoRA, SparseCtrl, sliding
 context windows, img2video, the diffusers MotionAdapter layout and GIF / MP4 writing are not built.
+
+``forward(..., upscale=True)`` (INTEGRATION.md "Upscaling (Real-ESRGAN)") sends the quantised images of every pipeline -- ``hires_size``
+results, the frames of a video and the pasted-back photo of the repaint path included -- through a Real-ESRGAN ``Upscaler``
+(``upscaler=`` at construction or ``load_upscaler``: an ``Upscaler``, an ``RRDBNet`` or a local ``.pth`` file; adaface/esrgan.py) on the
+device before they become PIL images.  Without a loaded upscaler, without a ``vae``, or for a result above the upscaler's 1024-pixel
+input limit it is a ValueError before any GPU work.  ``upscale=False`` is the call as it was.
 
 SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, U-Net ensembles and the
 ``forward(photo, ..., mask_image="face", crop_padding=0.5)`` (``inpaint`` only; INTEGRATION.md "Repainting faces in a photo") repaints
@@ -218,7 +225,7 @@ class AdaFaceWrapper(nn.Module):
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
                  lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None, face_detector=None, motion_module_path=None,
-                 beta_schedule="linear"):
+                 beta_schedule="linear", upscaler=None):
         super().__init__()
         if pipeline_name not in ("text2img", "img2img", "inpaint", None):
             raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img, img2img and inpaint paths (and None = face "
@@ -273,6 +280,7 @@ class AdaFaceWrapper(nn.Module):
             raise ValueError("beta_schedule is given together with a ready ldm: build that LatentDiffusion with the schedule instead")
         # beta_schedule: make_beta_schedule's names -- "linear" is SD's scaled-linear table, "sqrt_linear" the plain-linear betas of AnimateDiff's configs
         self.ldm = None if pipeline_name is None else (ldm or LatentDiffusion(unet_config or SD15_UNET_CONFIG, beta_schedule=beta_schedule))
+        self.__dict__["upscaler"] = None          # an esrgan.Upscaler (load_upscaler) for forward(upscale=True); not a submodule
         self.__dict__["motion_module"] = None     # a MotionModule (load_motion_module); not a submodule: it is on the U-Net only inside forward(num_frames=F)
         self.vae = vae
         self.img_prompt_embs = None
@@ -287,6 +295,8 @@ class AdaFaceWrapper(nn.Module):
             self.load_subj_basis_generator(adaface_ckpt_paths)
         if motion_module_path is not None:
             self.load_motion_module(motion_module_path)
+        if upscaler is not None:
+            self.load_upscaler(upscaler)
 
     # ------------------------------------------------------------------ checkpoints
     def load_base_model(self, base_model_path):
@@ -326,6 +336,29 @@ class AdaFaceWrapper(nn.Module):
         self.__dict__["motion_module"] = None
         if self.ldm is not None:
             self.ldm.model.diffusion_model.set_motion(None)
+
+    def load_upscaler(self, path_or_net):
+        """A Real-ESRGAN upscaler for ``forward(..., upscale=True)`` (adaface/esrgan.py; INTEGRATION.md "Upscaling (Real-ESRGAN)"): an
+        ``Upscaler``, an ``RRDBNet``, or a local ``.pth`` file / state dict (loaded strictly by ``load_esrgan``).  Nothing is downloaded."""
+        from . import esrgan
+        up = path_or_net
+        if not isinstance(up, esrgan.Upscaler):
+            net = up if isinstance(up, esrgan.RRDBNet) else esrgan.load_esrgan(up)
+            up = esrgan.Upscaler(net, device=self.device)
+        self.__dict__["upscaler"] = up
+        return up
+
+    def unload_upscaler(self):
+        self.__dict__["upscaler"] = None
+
+    def _check_upscale(self, H, W):
+        """The refusals of forward(upscale=True) for a result of H x W pixels, all ValueError before any GPU work."""
+        if self.upscaler is None:
+            raise ValueError("upscale=True but no upscaler is loaded (upscaler= at construction / load_upscaler)")
+        if self.vae is None:
+            raise ValueError("upscale=True needs a vae: without one forward returns latents, which are not upscaled")
+        if H is not None:
+            self.upscaler.check_size(int(H), int(W))
 
     def _check_video(self, noise, num_frames, out_image_count, hires_size):
         """The refusals of forward(num_frames=F) (INTEGRATION.md "Video (motion modules)"), all before any GPU work."""
@@ -495,9 +528,11 @@ class AdaFaceWrapper(nn.Module):
                 ablate_prompt_no_placeholders=False, ablate_prompt_embed_type="ada", nonmix_prompt_emb_weight=0,
                 repeat_prompt_for_each_encoder=True, verbose=False, mask_image=None, hires_size=None, hires_strength=0.7,
                 hires_steps=None, hires_upscaler="bilinear", crop_padding=None, face_index=None, face_mask_expand=1.3,
-                face_mask_feather=0.25, work_size=None, num_frames=None):
+                face_mask_feather=0.25, work_size=None, num_frames=None, upscale=False):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
+        if upscale:
+            self._check_upscale(None, None)
         if num_frames is not None:
             self._check_video(noise, num_frames, out_image_count, hires_size)
             videos = out_image_count
@@ -505,6 +540,11 @@ class AdaFaceWrapper(nn.Module):
         repaint = self._check_repaint(noise, mask_image, crop_padding, face_index, face_mask_expand, face_mask_feather, work_size)
         if hires_size is not None:
             hires_hw, hires_steps = self._check_hires(hires_size, hires_strength, hires_steps, hires_upscaler)
+        if upscale and self.pipeline_name == "text2img":
+            if hires_size is not None:
+                self._check_upscale(hires_hw[0] * 8, hires_hw[1] * 8)
+            elif torch.is_tensor(noise) and noise.dim() == 4:
+                self._check_upscale(noise.shape[2] * 8, noise.shape[3] * 8)
         inpaint = self.pipeline_name == "inpaint"
         if inpaint and mask_image is None:
             raise ValueError("the inpaint pipeline needs mask_image (white = repaint)")
@@ -516,13 +556,15 @@ class AdaFaceWrapper(nn.Module):
                                  f"decoder) as vae, got {type(self.vae).__name__ if self.vae is not None else None}")
             if repaint is not None:
                 self._sampler().img2img_steps(self.num_inference_steps, ref_img_strength)    # (before the detector runs)
-                repaint = self._repaint_plan(noise, mask_image, out_image_count, repaint)
+                repaint = self._repaint_plan(noise, mask_image, out_image_count, repaint, upscale)
                 images_u8 = None
             else:
                 images_u8 = img2img_images_u8(noise, out_image_count)
             if images_u8 is not None and max(images_u8.shape[1:3]) > MAX_IMAGE_SIDE:
                 raise ValueError(f"{self.pipeline_name} input images may be at most {MAX_IMAGE_SIDE} pixels on a side (the VAE's limit), got "
                                  f"{images_u8.shape[2]} x {images_u8.shape[1]}")
+            if upscale and images_u8 is not None:
+                self._check_upscale(images_u8.shape[1], images_u8.shape[2])
             if inpaint and repaint is None:
                 masks = inpaint_masks(mask_image, out_image_count, (images_u8.shape[2], images_u8.shape[1]))
             self._sampler().img2img_steps(self.num_inference_steps, ref_img_strength)    # refuse a bad strength before any work
@@ -552,7 +594,7 @@ class AdaFaceWrapper(nn.Module):
                                            first_stage_model=self.vae)
             latents, _ = sampler.sample_img2img(self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond,
                                                 guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
-            return self._to_pil(latents)
+            return self._to_pil(latents, upscale)
         if inpaint:
             _, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
             if repaint is not None:
@@ -568,8 +610,8 @@ class AdaFaceWrapper(nn.Module):
                                                 masks.to(self.device), cond, guidance_scale=guidance_scale,
                                                 unconditional_conditioning=uncond, generator=generator)
             if repaint is not None:
-                return self._paste_back(latents, photo, alpha, repaint["rect"])
-            return self._to_pil(latents)
+                return self._paste_back(latents, photo, alpha, repaint["rect"], upscale)
+            return self._to_pil(latents, upscale)
         noise = noise.to(device=self.device, dtype=torch.float32)
         unet = self.ldm.model.diffusion_model
         if num_frames is not None:
@@ -589,9 +631,9 @@ class AdaFaceWrapper(nn.Module):
         if self.vae is None:
             return latents
         if num_frames is not None:
-            frames = self._to_pil(latents)
+            frames = self._to_pil(latents, upscale)
             return [frames[v * num_frames:(v + 1) * num_frames] for v in range(videos)]
-        return self._to_pil(latents)
+        return self._to_pil(latents, upscale)
 
     def _check_hires(self, hires_size, hires_strength, hires_steps, hires_upscaler):
         """The refusals of high-resolution text2img (INTEGRATION.md "High-resolution text2img"), all before any GPU work.  Returns
@@ -654,7 +696,7 @@ class AdaFaceWrapper(nn.Module):
         return dict(face=face, crop_padding=crop_padding, face_index=face_index, expand=float(face_mask_expand),
                     feather=float(face_mask_feather), work_hw=work_hw)
 
-    def _repaint_plan(self, photo, mask_image, out_image_count, cfg):
+    def _repaint_plan(self, photo, mask_image, out_image_count, cfg, upscale=False):
         """Host preparation of the photo-level path: the photo's bytes, the ellipses (or the hard mask), the rectangle and the working
         size.  The detector is the only GPU work in here."""
         from PIL import Image
@@ -667,6 +709,8 @@ class AdaFaceWrapper(nn.Module):
                 raise ValueError(f"without crop_padding the whole photo is repainted: it may be at most {MAX_IMAGE_SIDE} pixels on a side "
                                  f"(the VAE's limit), got {rgb.shape[1]} x {rgb.shape[0]}; pass crop_padding to repaint a region")
         H, W = rgb.shape[:2]
+        if upscale:                                 # the photo comes back upscaled: refuse its size before the detector runs
+            self._check_upscale(H, W)
         if H * W * 3 >= 1 << 31:
             raise ValueError(f"the photo needs 2^31 bytes or more ({W} x {H}): the kernels use 32-bit offsets")
         plan = dict(photo=rgb, ellipses=None, hard_mask=None, feather=cfg["feather"])
@@ -690,12 +734,16 @@ class AdaFaceWrapper(nn.Module):
             plan["rect"] = face_repaint.crop_region(boxes, (H, W), cfg["work_hw"], cfg["crop_padding"])
         return plan
 
-    def _paste_back(self, latents, photo, alpha, rect):
-        """Decode, then one ``ops.paste_back_u8`` launch and one device-to-host copy (per slice of photos that stays below 2^31 bytes)."""
+    def _paste_back(self, latents, photo, alpha, rect, upscale=False):
+        """Decode, then one ``ops.paste_back_u8`` launch and one device-to-host copy (per slice of photos that stays below 2^31 bytes); under
+        ``upscale`` the pasted photos go through the upscaler on the device in between."""
         from PIL import Image
         decoded = self._decode(latents).float().contiguous()
         per = max(1, (2 ** 31 - 1) // photo.numel())
-        out = [ops.paste_back_u8(decoded[i:i + per], photo, alpha, rect).cpu().numpy() for i in range(0, decoded.shape[0], per)]
+        out = []
+        for i in range(0, decoded.shape[0], per):
+            part = ops.paste_back_u8(decoded[i:i + per], photo, alpha, rect)
+            out.append((self.upscaler.upscale_u8(part) if upscale else part).cpu().numpy())
         return [Image.fromarray(im) for part in out for im in part]
 
     def _sampler(self):
@@ -707,8 +755,11 @@ class AdaFaceWrapper(nn.Module):
         per = max(1, (2 ** 31 - 1) // (latents.shape[2] * latents.shape[3] * 64 * 256))
         return torch.cat([self.vae.decode(latents[i:i + per] / 0.18215) for i in range(0, latents.shape[0], per)])
 
-    def _to_pil(self, latents):
+    def _to_pil(self, latents, upscale=False):
         images = self._decode(latents)
-        images = ((images.float() / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+        images = ((images.float() / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1)
+        if upscale:                                 # on the device, in slices of images (Upscaler.upscale_u8): no host round trip
+            images = self.upscaler.upscale_u8(images.contiguous())
+        images = images.cpu().numpy()
         from PIL import Image
         return [Image.fromarray(im) for im in images]

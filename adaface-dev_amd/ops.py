@@ -1565,6 +1565,69 @@ def paste_back_u8(decoded, photo_u8, alpha, rect):
     return out
 
 
+# ----------------------------------------------------------------------------- Real-ESRGAN (adaface/esrgan.py)
+def _chk_nhwc_buf(t, name):
+    if t.dtype != F16 or not t.is_cuda or not t.is_contiguous() or t.dim() != 4 or t.numel() == 0:
+        raise RuntimeError(f"{name}: expected a non-empty contiguous fp16 device tensor [B, H, W, ld], got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _slice_ptr(t, ch, cout, grid, name):
+    """Address of channel ``ch`` of the NHWC buffer ``t`` (whose [B, H, W] must be ``grid``) and its row stride."""
+    _chk_nhwc_buf(t, name)
+    if tuple(t.shape[:3]) != tuple(grid) or ch < 0 or ch % 8 or ch + cout > t.shape[3]:
+        raise RuntimeError(f"{name}: channels [{ch}, {ch + cout}) of {tuple(t.shape)} do not fit the output grid {tuple(grid)} (the offset "
+                           "must be a multiple of 8)")
+    return t.data_ptr() + 2 * ch, t.shape[3]
+
+
+def dense_conv3x3_weight(weight: torch.Tensor, cin_pad: Optional[int] = None) -> torch.Tensor:
+    """A torch conv weight [cout, cin, 3, 3] -> af_dense_conv3x3's fp16 [npad][9 * cin_pad] (K order (ky, kx, c)), npad = cout rounded up to
+    16, input channels zero-padded to ``cin_pad`` (default: cin rounded up to 32)."""
+    cout, cin = weight.shape[:2]
+    cp = cin_pad if cin_pad is not None else (cin + 31) // 32 * 32
+    w = torch.zeros(((cout + 15) // 16 * 16, 3, 3, cp), dtype=F16, device=weight.device)
+    w[:cout, :, :, :cin] = weight.permute(0, 2, 3, 1).to(F16)
+    return w.reshape(w.shape[0], 9 * cp).contiguous()
+
+
+def dense_conv3x3(x, cin, wt, bias, out, out_ch, cout, r1=None, r1_ch=0, alpha=1.0, r2=None, r2_ch=0, beta=1.0, slope=0.0, upsample=False):
+    """One af_dense_conv3x3 launch: the 3x3 convolution (pad 1) of channels [0, cin) of the NHWC buffer ``x`` [B, H, W, ldx] (nearest-x2
+    upsampled first under ``upsample``, never materialised) written to channels [out_ch, out_ch + cout) of ``out`` [B, Ho, Wo, ldo], which
+    may be ``x`` itself on channels behind cin.  v = lrelu(conv + bias, slope); with r1: v = alpha v + r1[..., r1_ch:]; with r2 too:
+    v = beta v + r2[..., r2_ch:].  Nothing else of ``out`` is written.  ``wt`` as dense_conv3x3_weight makes it, ``bias`` fp32 [cout] or None."""
+    _chk_nhwc_buf(x, "dense_conv3x3.x")
+    B, H, W, ldx = x.shape
+    grid = (B, 2 * H, 2 * W) if upsample else (B, H, W)
+    po, ldo = _slice_ptr(out, out_ch, cout, grid, "dense_conv3x3.out")
+    p1, ld1 = _slice_ptr(r1, r1_ch, cout, grid, "dense_conv3x3.r1") if r1 is not None else (None, 0)
+    p2, ld2 = _slice_ptr(r2, r2_ch, cout, grid, "dense_conv3x3.r2") if r2 is not None else (None, 0)
+    _lib.check(_lib.lib().af_dense_conv3x3(_p(x), ldx, cin, _p(wt), _p(bias), po, ldo, cout, p1, ld1, alpha, p2, ld2, beta, slope,
+                                           int(upsample), 0, B, H, W, _stream()), "af_dense_conv3x3")
+    return out
+
+
+def dense_conv3x3_u8(x, cin, wt, bias, cout, slope=0.0, upsample=False):
+    """As dense_conv3x3 with the uint8 epilogue: a new tight uint8 [B, Ho, Wo, cout] = rint(255 clamp(v, 0, 1)), ties to even."""
+    _chk_nhwc_buf(x, "dense_conv3x3_u8.x")
+    B, H, W, ldx = x.shape
+    s = 2 if upsample else 1
+    out = torch.empty((B, s * H, s * W, cout), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().af_dense_conv3x3(_p(x), ldx, cin, _p(wt), _p(bias), _p(out), 0, cout, None, 0, 1.0, None, 0, 1.0, slope,
+                                           int(upsample), 1, B, H, W, _stream()), "af_dense_conv3x3")
+    return out
+
+
+def u8_unshuffle_f16(img_u8: torch.Tensor, r: int, cpad: int) -> torch.Tensor:
+    """uint8 RGB [B, H, W, 3] -> fp16 [B, H / r, W / r, cpad]: pixel_unshuffle(img / 255, r) in torch's channel order, zeros behind 3 r^2."""
+    if img_u8.dtype != torch.uint8 or not img_u8.is_cuda or not img_u8.is_contiguous() or img_u8.dim() != 4 or img_u8.shape[3] != 3:
+        raise RuntimeError(f"u8_unshuffle_f16: expected a contiguous uint8 device tensor [B, H, W, 3], got {img_u8.dtype} "
+                           f"{tuple(img_u8.shape)} on {img_u8.device}")
+    B, H, W, _ = img_u8.shape
+    out = torch.empty((B, H // max(r, 1), W // max(r, 1), cpad), dtype=F16, device=img_u8.device)
+    _lib.check(_lib.lib().af_u8_unshuffle_f16(_p(img_u8), _p(out), B, H, W, r, cpad, _stream()), "af_u8_unshuffle_f16")
+    return out
+
+
 # ----------------------------------------------------------------------------- profiling hook
 def prof_enable(on: bool):
     _lib.check(_lib.lib().af_prof_enable(int(on)), "af_prof_enable")

@@ -588,6 +588,28 @@ int af_crop_resize_u8(const void* photo_u8, const void* alpha, void* image_u8, v
 int af_paste_back_u8(const void* decoded, const void* photo_u8, const void* alpha, void* out_u8, int B, int Hs, int Ws, int H, int W, int x0,
                      int y0, int cw, int ch, void* stream);
 
+/* ---- Real-ESRGAN upscaler (adaface/esrgan.py, RRDBNet): a 3x3 convolution (pad 1) that reads the first cin channels of a strided NHWC buffer
+ * and writes a narrow channel slice of the same or another buffer, so that a dense block's concatenation is a buffer layout and never a copy.
+ * y[b,i,j,n] = bias[n] + sum_{ky,kx,c<cin} wt[n][(ky*3+kx)*cin + c] * X[b, i+ky-1, j+kx-1, c]      (zero outside the image)
+ *   X[b,i,j,c] = x[((b*H + i)*W + j)*ldx + c]                        upsample == 0, output Ho x Wo = H x W
+ *   X[b,i,j,c] = x[((b*H + (i>>1))*W + (j>>1))*ldx + c], 0 <= i < 2H  upsample == 1 (nearest x2, not materialised), output 2H x 2W
+ * v = slope > 0 ? (y >= 0 ? y : slope*y) : y ;  if r1: v = alpha*v + r1[m*ldr1 + n] ;  if r2: v = beta*v + r2[m*ldr2 + n]   (all fp32)
+ * out_mode 0: out fp16, out[m*ldo + n] = fp16(v) for n < cout.  Channels >= cout of the row and any bytes between rows are NOT written.
+ * out_mode 1: out uint8 [M][cout] tight (ldo ignored), out = rint(255 * min(max(v, 0), 1)), round-half-even.
+ * x fp16, cin % 32 == 0, 32 <= cin <= 192, ldx >= cin.  wt fp16 [npad][9*cin], npad = cout rounded up to 16, zero rows behind cout.
+ * 1 <= cout <= 64.  bias fp32 [cout] or NULL.  ldx, ldo, ldr1, ldr2 % 8 == 0, 16-byte aligned pointers.
+ * out may lie in x's buffer on channels disjoint from [0, cin) (the dense-block write: same row stride, same grid).  r1 / r2 may be exactly
+ * the out elements, or other channels of out's rows (same row stride); any other overlap of their byte range with out's is refused.  That
+ * out does not overlap wt or bias is the caller's duty (not checked).
+ * AF_E_BADARG before any launch: NULL x / wt / out, a size outside the above, an out range that overlaps channels [0, cin) of x,
+ * r1 / r2 overlapping out otherwise than stated, r2 without r1, B*H*W*ldx or B*Ho*Wo*max(ldo, ldr1, ldr2, cout) at or above 2^31.  No workspace, one launch. */
+int af_dense_conv3x3(const void* x, int ldx, int cin, const void* wt, const void* bias, void* out, int ldo, int cout,
+                     const void* r1, int ldr1, float alpha, const void* r2, int ldr2, float beta, float slope,
+                     int upsample, int out_mode, int B, int H, int W, void* stream);
+/* img uint8 [B, H, W, 3] -> out fp16 [B, H/r, W/r, cpad]: channel c*r*r + dy*r + dx = img[b, i*r+dy, j*r+dx, c] / 255 (torch's pixel_unshuffle
+ * order), channels 3 r^2 .. cpad zero.  r in {1, 2, 4}, H % r == W % r == 0, cpad in {32, 64} and >= 3 r^2; fewer than 2^31 elements each side. */
+int af_u8_unshuffle_f16(const void* img_u8, void* out, int B, int H, int W, int r, int cpad, void* stream);
+
 /* ---- trainable DoRA adapters on the U-Net's up_blocks.3 convolutions (adaface/diffusers_attn_lora_capture.py:541-591; peft
  * DoraConv2dLayer.forward: y = base(x) + (s - 1) * conv(xd, W) + s * scaling * B(A(xd)), xd = dropout(x)) ---------------------
  * out = y0 + u[c] * c2 + v[c] * lb   (fp16 [rows, C]; u = s - 1, v = s * scaling, fp32 [C]) */
