@@ -40,6 +40,7 @@ EXPORTS = (
     "af_face_alpha_mask", "af_crop_resize_u8", "af_paste_back_u8",
     "af_temporal_attention",
     "af_dense_conv3x3", "af_u8_unshuffle_f16",
+    "af_modulate_weights", "af_style_epilogue", "af_bilinear_up2", "af_face_paste_affine_u8", "af_face_align_crop_any",
 )
 
 
@@ -170,6 +171,11 @@ def lib() -> C.CDLL:
     L.af_temporal_attention.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
     L.af_dense_conv3x3.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, f32, vp, i32, f32, f32, i32, i32, i32, i32, i32, vp]
     L.af_u8_unshuffle_f16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    L.af_modulate_weights.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
+    L.af_style_epilogue.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]
+    L.af_bilinear_up2.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    L.af_face_paste_affine_u8.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]
+    L.af_face_align_crop_any.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.af_prefetch.argtypes = [vp, i64, vp]
     L.af_prefetch_ex.argtypes = [vp, i64, i32, vp]
     L.af_xattn_scores.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]

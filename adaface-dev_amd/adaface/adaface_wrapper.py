@@ -67,6 +67,11 @@ results, the frames of a video and the pasted-back photo of the repaint path inc
 device before they become PIL images.  Without a loaded upscaler, without a ``vae``, or for a result above the upscaler's 1024-pixel
 input limit it is a ValueError before any GPU work.  ``upscale=False`` is the call as it was.
 
+``forward(..., restore_faces=True)`` (INTEGRATION.md "Face restoration (GFPGAN)") sends the same quantised images through a GFPGAN
+``FaceRestorer`` (``face_restorer=`` at construction or ``load_face_restorer``; adaface/gfpgan.py) on the device, BEFORE the upscaler and
+before they become PIL images: every detected face is aligned, restored and pasted back with a soft border.  Without a loaded restorer or
+without a ``vae`` it is a ValueError before any GPU work.  ``restore_faces=False`` is the call as it was.
+
 SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, U-Net ensembles and the
 ``forward(photo, ..., mask_image="face", crop_padding=0.5)`` (``inpaint`` only; INTEGRATION.md "Repainting faces in a photo") repaints
 the faces of ONE photo of any size (a PIL image, a path or a uint8 array) and hands back the same photo: ``face_detector`` (any callable
@@ -225,7 +230,7 @@ class AdaFaceWrapper(nn.Module):
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
                  lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None, face_detector=None, motion_module_path=None,
-                 beta_schedule="linear", upscaler=None):
+                 beta_schedule="linear", upscaler=None, face_restorer=None):
         super().__init__()
         if pipeline_name not in ("text2img", "img2img", "inpaint", None):
             raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img, img2img and inpaint paths (and None = face "
@@ -281,6 +286,7 @@ class AdaFaceWrapper(nn.Module):
         # beta_schedule: make_beta_schedule's names -- "linear" is SD's scaled-linear table, "sqrt_linear" the plain-linear betas of AnimateDiff's configs
         self.ldm = None if pipeline_name is None else (ldm or LatentDiffusion(unet_config or SD15_UNET_CONFIG, beta_schedule=beta_schedule))
         self.__dict__["upscaler"] = None          # an esrgan.Upscaler (load_upscaler) for forward(upscale=True); not a submodule
+        self.__dict__["face_restorer"] = None     # a gfpgan.FaceRestorer (load_face_restorer) for forward(restore_faces=True); not a submodule
         self.__dict__["motion_module"] = None     # a MotionModule (load_motion_module); not a submodule: it is on the U-Net only inside forward(num_frames=F)
         self.vae = vae
         self.img_prompt_embs = None
@@ -297,6 +303,8 @@ class AdaFaceWrapper(nn.Module):
             self.load_motion_module(motion_module_path)
         if upscaler is not None:
             self.load_upscaler(upscaler)
+        if face_restorer is not None:
+            self.load_face_restorer(face_restorer)
 
     # ------------------------------------------------------------------ checkpoints
     def load_base_model(self, base_model_path):
@@ -350,6 +358,35 @@ class AdaFaceWrapper(nn.Module):
 
     def unload_upscaler(self):
         self.__dict__["upscaler"] = None
+
+    def load_face_restorer(self, path_or_net, detect_faces=None, **kwargs):
+        """A GFPGAN face restorer for ``forward(..., restore_faces=True)`` (adaface/gfpgan.py; INTEGRATION.md "Face restoration (GFPGAN)"): a
+        ``FaceRestorer``, a ``GFPGANv1Clean``, or a local ``.pth`` file / state dict (loaded strictly by ``load_gfpgan``).  The detector is
+        ``detect_faces`` or, by default, the wrapper's ``face_detector``; ``kwargs`` go to ``FaceRestorer``.  Nothing is downloaded."""
+        from . import gfpgan
+        fr = path_or_net
+        if not isinstance(fr, gfpgan.FaceRestorer):
+            net = fr if isinstance(fr, gfpgan.GFPGANv1Clean) else gfpgan.load_gfpgan(fr)
+            detect = detect_faces if detect_faces is not None else self.face_detector
+            if detect is None:
+                raise ValueError("a face restorer needs a detector: pass detect_faces, or build the wrapper with face_detector / face_id_extractor")
+            fr = gfpgan.FaceRestorer(net, detect, device=self.device, **kwargs)
+        self.__dict__["face_restorer"] = fr
+        return fr
+
+    def unload_face_restorer(self):
+        self.__dict__["face_restorer"] = None
+
+    def _check_restore(self):
+        """The refusals of forward(restore_faces=True), ValueError before any GPU work."""
+        if self.face_restorer is None:
+            raise ValueError("restore_faces=True but no face restorer is loaded (face_restorer= at construction / load_face_restorer)")
+        if self.vae is None:
+            raise ValueError("restore_faces=True needs a vae: without one forward returns latents, which show no faces")
+
+    def _restore(self, images_u8):
+        """uint8 device images [B, H, W, 3] -> the same with every detected face restored (image by image: the detector takes one)."""
+        return torch.stack([self.face_restorer.restore_u8(im) for im in images_u8])
 
     def _check_upscale(self, H, W):
         """The refusals of forward(upscale=True) for a result of H x W pixels, all ValueError before any GPU work."""
@@ -528,11 +565,13 @@ class AdaFaceWrapper(nn.Module):
                 ablate_prompt_no_placeholders=False, ablate_prompt_embed_type="ada", nonmix_prompt_emb_weight=0,
                 repeat_prompt_for_each_encoder=True, verbose=False, mask_image=None, hires_size=None, hires_strength=0.7,
                 hires_steps=None, hires_upscaler="bilinear", crop_padding=None, face_index=None, face_mask_expand=1.3,
-                face_mask_feather=0.25, work_size=None, num_frames=None, upscale=False):
+                face_mask_feather=0.25, work_size=None, num_frames=None, upscale=False, restore_faces=False):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
         if upscale:
             self._check_upscale(None, None)
+        if restore_faces:
+            self._check_restore()
         if num_frames is not None:
             self._check_video(noise, num_frames, out_image_count, hires_size)
             videos = out_image_count
@@ -594,7 +633,7 @@ class AdaFaceWrapper(nn.Module):
                                            first_stage_model=self.vae)
             latents, _ = sampler.sample_img2img(self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond,
                                                 guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
-            return self._to_pil(latents, upscale)
+            return self._to_pil(latents, upscale, restore_faces)
         if inpaint:
             _, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
             if repaint is not None:
@@ -610,8 +649,8 @@ class AdaFaceWrapper(nn.Module):
                                                 masks.to(self.device), cond, guidance_scale=guidance_scale,
                                                 unconditional_conditioning=uncond, generator=generator)
             if repaint is not None:
-                return self._paste_back(latents, photo, alpha, repaint["rect"], upscale)
-            return self._to_pil(latents, upscale)
+                return self._paste_back(latents, photo, alpha, repaint["rect"], upscale, restore_faces)
+            return self._to_pil(latents, upscale, restore_faces)
         noise = noise.to(device=self.device, dtype=torch.float32)
         unet = self.ldm.model.diffusion_model
         if num_frames is not None:
@@ -631,9 +670,9 @@ class AdaFaceWrapper(nn.Module):
         if self.vae is None:
             return latents
         if num_frames is not None:
-            frames = self._to_pil(latents, upscale)
+            frames = self._to_pil(latents, upscale, restore_faces)
             return [frames[v * num_frames:(v + 1) * num_frames] for v in range(videos)]
-        return self._to_pil(latents, upscale)
+        return self._to_pil(latents, upscale, restore_faces)
 
     def _check_hires(self, hires_size, hires_strength, hires_steps, hires_upscaler):
         """The refusals of high-resolution text2img (INTEGRATION.md "High-resolution text2img"), all before any GPU work.  Returns
@@ -734,15 +773,17 @@ class AdaFaceWrapper(nn.Module):
             plan["rect"] = face_repaint.crop_region(boxes, (H, W), cfg["work_hw"], cfg["crop_padding"])
         return plan
 
-    def _paste_back(self, latents, photo, alpha, rect, upscale=False):
+    def _paste_back(self, latents, photo, alpha, rect, upscale=False, restore_faces=False):
         """Decode, then one ``ops.paste_back_u8`` launch and one device-to-host copy (per slice of photos that stays below 2^31 bytes); under
-        ``upscale`` the pasted photos go through the upscaler on the device in between."""
+        ``restore_faces`` and ``upscale`` the pasted photos go through the face restorer and then the upscaler on the device in between."""
         from PIL import Image
         decoded = self._decode(latents).float().contiguous()
         per = max(1, (2 ** 31 - 1) // photo.numel())
         out = []
         for i in range(0, decoded.shape[0], per):
             part = ops.paste_back_u8(decoded[i:i + per], photo, alpha, rect)
+            if restore_faces:
+                part = self._restore(part)
             out.append((self.upscaler.upscale_u8(part) if upscale else part).cpu().numpy())
         return [Image.fromarray(im) for part in out for im in part]
 
@@ -755,9 +796,11 @@ class AdaFaceWrapper(nn.Module):
         per = max(1, (2 ** 31 - 1) // (latents.shape[2] * latents.shape[3] * 64 * 256))
         return torch.cat([self.vae.decode(latents[i:i + per] / 0.18215) for i in range(0, latents.shape[0], per)])
 
-    def _to_pil(self, latents, upscale=False):
+    def _to_pil(self, latents, upscale=False, restore_faces=False):
         images = self._decode(latents)
         images = ((images.float() / 2 + 0.5).clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1)
+        if restore_faces:                           # before the upscaler: it sharpens what the restorer leaves, artefacts included
+            images = self._restore(images.contiguous())
         if upscale:                                 # on the device, in slices of images (Upscaler.upscale_u8): no host round trip
             images = self.upscaler.upscale_u8(images.contiguous())
         images = images.cpu().numpy()

@@ -307,6 +307,21 @@ extern "C" int af_face_align_crop(const void* image_u8, const void* inv_mats, vo
   return af_check_launch("af_face_align_crop");
 }
 
+// the same kernel at the face restorer's crop sizes (adaface/gfpgan.py): any multiple of 8 up to 1024
+extern "C" int af_face_align_crop_any(const void* image_u8, const void* inv_mats, void* out, int H, int W, int F, int size, void* stream) {
+  AF_REQUIRE(image_u8 && inv_mats && out && H > 0 && W > 0, "af_face_align_crop_any: bad argument");
+  AF_REQUIRE((long)H * W * 3 < (1L << 31), "af_face_align_crop_any: the image needs fewer than 2^31 bytes (H * W * 3)");
+  AF_REQUIRE(F >= 1, "af_face_align_crop_any: at least one face");
+  AF_REQUIRE(size >= 8 && size <= 1024 && size % 8 == 0, "af_face_align_crop_any: size must be a multiple of 8 from 8 to 1024");
+  AF_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "af_face_align_crop_any: out must be 16-byte aligned");
+  const long npix = (long)F * size * size;
+  AF_REQUIRE(npix * 8 < (1L << 31), "af_face_align_crop_any: the crops need fewer than 2^31 elements (F * size^2 * 8)");
+  AfLaunchScope scope(AF_FAM_ELEM, stream);
+  hipLaunchKernelGGL(face_align_crop_kernel, g1(npix), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)image_u8,
+                     (const float*)inv_mats, (half_t*)out, H, W, size, npix);
+  return af_check_launch("af_face_align_crop_any");
+}
+
 extern "C" int af_maxpool2x2(const void* x, void* y, int B, int Ho, int Wo, int C, void* stream) {
   AF_REQUIRE(x && y && B > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 8 == 0, "af_maxpool2x2: bad argument");
   AfLaunchScope scope(AF_FAM_ELEM, stream);

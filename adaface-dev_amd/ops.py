@@ -422,10 +422,12 @@ def _launch_gemm(d: "GemmDesc", device, what: str, tile: int = 0, splits: int = 
 # ----------------------------------------------------------------------------- gemm / conv
 def gemm(a1: torch.Tensor, pw: PackedWeight, *, a2: Optional[torch.Tensor] = None, rowbias: Optional[torch.Tensor] = None,
          rows_per_batch: int = 0, residual: Optional[torch.Tensor] = None, act: int = AF_ACT_NONE,
-         split_col: int = 0, ld_out2: int = 0, tile: int = 0, splits: int = 0, out_f32: bool = False, gn_cpg: int = 0):
+         split_col: int = 0, ld_out2: int = 0, tile: int = 0, splits: int = 0, out_f32: bool = False, gn_cpg: int = 0,
+         out: Optional[torch.Tensor] = None):
     """Plain-rows GEMM: a1 [M, K1] (+ a2 [M, K2], concatenated along K) x pw.  Returns out
     ([M, N], or [M, N/2] for GEGLU), or (out [M, split_col], out2 [B, N-split_col, ld_out2]).  out_f32: the fp32 accumulator is
-    returned (AF_OUT_F32; weight gradients)."""
+    returned (AF_OUT_F32; weight gradients).  out: a contiguous fp16 [M, N] tensor to write instead of a fresh one (standard epilogue only)
+    -- a slice of a batch's output when the weights differ per sample (adaface/gfpgan.py)."""
     _chk_f16(a1, "gemm.a1")
     M, k1 = a1.shape
     k2 = 0
@@ -434,6 +436,7 @@ def gemm(a1: torch.Tensor, pw: PackedWeight, *, a2: Optional[torch.Tensor] = Non
         k2 = a2.shape[1]
         assert a2.shape[0] == M
     assert k1 + k2 == pw.K, f"gemm: K mismatch {k1}+{k2} vs {pw.K}"
+    assert out is None or not (split_col or out_f32), "gemm: out= goes with the standard fp16 epilogue only"
     d = GemmDesc()
     d.a1, d.a2, d.wt, d.bias = _p(a1), _p(a2), _p(pw.wt), _p(pw.bias)
     d.rowbias, d.residual = _p(rowbias), _p(residual)
@@ -457,6 +460,9 @@ def gemm(a1: torch.Tensor, pw: PackedWeight, *, a2: Optional[torch.Tensor] = Non
         assert act == AF_ACT_NONE and pw.N % 4 == 0
         out = torch.empty((M, pw.N), dtype=torch.float32, device=a1.device)
         d.out_mode = AF_OUT_F32
+    elif out is not None:
+        _chk_f16(out, "gemm.out")
+        assert act != AF_ACT_GEGLU and tuple(out.shape) == (M, pw.N), f"gemm: out must be [{M}, {pw.N}], got {tuple(out.shape)}"
     else:
         n_out = pw.N // 2 if act == AF_ACT_GEGLU else pw.N
         out = torch.empty((M, n_out), dtype=F16, device=a1.device)
@@ -487,10 +493,10 @@ def _whole_line_tile(M: int, N: int) -> int:
 
 def conv3x3(x: torch.Tensor, pw: PackedWeight, *, x2: Optional[torch.Tensor] = None, stride: int = 1, upsample: bool = False,
             rowbias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, tile: int = 0,
-            splits: int = 0, out_hw=None, tap_shift: int = 0, skip=None, gn_cpg: int = 0) -> torch.Tensor:
+            splits: int = 0, out_hw=None, tap_shift: int = 0, skip=None, gn_cpg: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """3x3 / pad 1 convolution as implicit GEMM (tap_shift=1: padding (0, 1, 0, 1) instead, the VAE encoder's Downsample).  x [B,H,W,C1] (+ x2 [B,H,W,C2] channel-concat)
     -> [B,Ho,Wo,Cout].  rowbias [B, >=Cout] is added per batch item (time-embedding), residual
-    [B,Ho,Wo,Cout] after it."""
+    [B,Ho,Wo,Cout] after it.  out: a contiguous fp16 [B,Ho,Wo,Cout] tensor to write instead of a fresh one."""
     _chk_f16(x, "conv3x3.x")
     B, H, W, c1 = x.shape
     c2 = 0
@@ -505,7 +511,11 @@ def conv3x3(x: torch.Tensor, pw: PackedWeight, *, x2: Optional[torch.Tensor] = N
     if int(upsample) == 2:      # zero-inserted image (stride-2 dgrad): output size = forward input size
         ho, wo = out_hw if out_hw is not None else (2 * H, 2 * W)
         assert ho in (2 * H, 2 * H - 1) and wo in (2 * W, 2 * W - 1)
-    out = torch.empty((B, ho, wo, pw.N), dtype=F16, device=x.device)
+    if out is None:
+        out = torch.empty((B, ho, wo, pw.N), dtype=F16, device=x.device)
+    else:
+        _chk_f16(out, "conv3x3.out")
+        assert tuple(out.shape) == (B, ho, wo, pw.N), f"conv3x3: out must be {(B, ho, wo, pw.N)}, got {tuple(out.shape)}"
     d = GemmDesc()
     d.a1, d.a2, d.wt, d.bias = _p(x), _p(x2), _p(pw.wt), _p(pw.bias)
     d.rowbias, d.residual, d.out = _p(rowbias), _p(residual), _p(out)
@@ -1304,6 +1314,111 @@ def face_align_crop(image_u8, inv_mats, size=112):
         raise RuntimeError(f"face_align_crop: size must be 112 or 128, got {size}")
     out = torch.empty((nf, size, size, 8), dtype=F16, device=image_u8.device)
     _lib.check(_lib.lib().af_face_align_crop(_p(image_u8), _p(inv_mats), _p(out), H, W, nf, size, _stream()), "af_face_align_crop")
+    return out
+
+
+def face_align_crop_any(image_u8, inv_mats, size):
+    """``face_align_crop`` at the face restorer's crop sizes (af_face_align_crop_any): any multiple of 8 from 8 to 1024."""
+    if image_u8.dtype != torch.uint8 or not image_u8.is_cuda or not image_u8.is_contiguous() or image_u8.dim() != 3 or image_u8.shape[2] != 3:
+        raise RuntimeError(f"face_align_crop_any: expected a contiguous uint8 device tensor [H, W, 3], got {image_u8.dtype} {tuple(image_u8.shape)} "
+                           f"on {image_u8.device}")
+    if (inv_mats.dtype != torch.float32 or inv_mats.device != image_u8.device or not inv_mats.is_contiguous() or inv_mats.dim() != 3
+            or tuple(inv_mats.shape[1:]) != (2, 3) or inv_mats.shape[0] < 1):
+        raise RuntimeError(f"face_align_crop_any.inv_mats: expected contiguous fp32 [F >= 1, 2, 3] on {image_u8.device}, got {inv_mats.dtype} "
+                           f"{tuple(inv_mats.shape)} on {inv_mats.device}")
+    H, W, _ = image_u8.shape
+    nf, size = inv_mats.shape[0], int(size)
+    if size < 8 or size > 1024 or size % 8:
+        raise RuntimeError(f"face_align_crop_any: size must be a multiple of 8 from 8 to 1024, got {size}")
+    out = torch.empty((nf, size, size, 8), dtype=F16, device=image_u8.device)
+    _lib.check(_lib.lib().af_face_align_crop_any(_p(image_u8), _p(inv_mats), _p(out), H, W, nf, size, _stream()), "af_face_align_crop_any")
+    return out
+
+
+# ----------------------------------------------------------------------------- GFPGAN face restorer (af_gfpgan.hip)
+def _chk_f32(t, shape, name, device):
+    if t.dtype != torch.float32 or t.device != device or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name}: expected contiguous fp32 {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def modulate_weights(w, wsq, styles, out, gain=1.0):
+    """Per-sample weights of a modulated convolution (af_modulate_weights): w fp32 [cout, taps, cin], wsq fp32 [cout, cin] or None (no
+    demodulation), styles fp32 [B, cin] -> out fp16 [B, npad, kpad] (the caller's buffer, zeroed once: only the cout x taps * cin block of every
+    slice is written), out[b, o, t * cin + i] = gain * d[b, o] * w[o, t, i] * styles[b, i]."""
+    cout, taps, cin = w.shape
+    B = styles.shape[0]
+    _chk_f32(w, (cout, taps, cin), "modulate_weights.w", out.device)
+    _chk_f32(styles, (B, cin), "modulate_weights.styles", out.device)
+    if wsq is not None:
+        _chk_f32(wsq, (cout, cin), "modulate_weights.wsq", out.device)
+    _chk_f16(out, "modulate_weights.out")
+    if out.dim() != 3 or out.shape[0] != B:
+        raise RuntimeError(f"modulate_weights.out: expected [{B}, npad, kpad], got {tuple(out.shape)}")
+    _lib.check(_lib.lib().af_modulate_weights(_p(w), _p(wsq), _p(styles), _p(out), B, cout, cin, taps, out.shape[1], out.shape[2],
+                                              int(wsq is not None), float(gain), _stream()), "af_modulate_weights")
+    return out
+
+
+def style_epilogue(y, noise=None, bias=None, scale=None, shift=None, nw=0.0, out=None):
+    """lrelu(y + nw * noise[p] + bias[c], 0.2), then v * scale + shift on the upper half of the channels, saturating at +-65504
+    (af_style_epilogue).  y fp16 [B, H, W, C] (or [B, HW, C]); noise fp32 with H * W elements; bias fp32 [C]; scale / shift fp16 [B, H, W, C / 2].
+    out=y works in place."""
+    _chk_f16(y, "style_epilogue.y")
+    B, Cn = y.shape[0], y.shape[-1]
+    hw = y.numel() // (B * Cn)
+    dev = y.device
+    if noise is not None:
+        _chk_f32(noise, noise.shape, "style_epilogue.noise", dev)
+        if noise.numel() != hw:
+            raise RuntimeError(f"style_epilogue.noise: expected {hw} elements, got {tuple(noise.shape)}")
+    if bias is not None:
+        _chk_f32(bias, (Cn,), "style_epilogue.bias", dev)
+    if (scale is None) != (shift is None):
+        raise RuntimeError("style_epilogue: scale and shift go together")
+    for name, t in (("scale", scale), ("shift", shift)):
+        if t is not None:
+            _chk_f16(t, "style_epilogue." + name)
+            if t.numel() != B * hw * (Cn // 2) or t.shape[-1] != Cn // 2 or Cn % 16:
+                raise RuntimeError(f"style_epilogue.{name}: expected [B, HW, C / 2] for y {tuple(y.shape)}, got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty_like(y)
+    else:
+        _chk_f16(out, "style_epilogue.out")
+        assert out.shape == y.shape
+    _lib.check(_lib.lib().af_style_epilogue(_p(y), _p(noise), _p(bias), _p(scale), _p(shift), _p(out), B, hw, Cn, float(nw), _stream()),
+               "af_style_epilogue")
+    return out
+
+
+def bilinear_up2(x, addend=None):
+    """fp16 [B, H, W, C] -> [B, 2H, 2W, C], torch's bilinear x2 with align_corners=False (+ addend) (af_bilinear_up2)."""
+    _chk_nhwc(x, "bilinear_up2.x")
+    B, H, W, Cn = x.shape
+    out = torch.empty((B, 2 * H, 2 * W, Cn), dtype=F16, device=x.device)
+    if addend is not None:
+        _chk_f16(addend, "bilinear_up2.addend")
+        if addend.shape != out.shape:
+            raise RuntimeError(f"bilinear_up2.addend: expected {tuple(out.shape)}, got {tuple(addend.shape)}")
+    _lib.check(_lib.lib().af_bilinear_up2(_p(x), _p(addend), _p(out), B, H, W, Cn, _stream()), "af_bilinear_up2")
+    return out
+
+
+def face_paste_affine_u8(photo_u8, crops, mats, erode, feather):
+    """Restored crops back into the photo (af_face_paste_affine_u8): photo uint8 [H, W, 3], crops fp16 [F, S, S, ld] or None, mats fp32
+    [F, 2, 3] (image -> crop) or None, erode / feather in crop pixels -> uint8 [H, W, 3]."""
+    _chk_photo(photo_u8, "face_paste_affine_u8.photo")
+    H, W, _ = photo_u8.shape
+    nf = 0 if crops is None else crops.shape[0]
+    out = torch.empty_like(photo_u8)
+    S = ld = 0
+    if nf:
+        _chk_f16(crops, "face_paste_affine_u8.crops")
+        if crops.dim() != 4 or crops.shape[1] != crops.shape[2] or crops.device != photo_u8.device:
+            raise RuntimeError(f"face_paste_affine_u8.crops: expected [F, S, S, ld] on {photo_u8.device}, got {tuple(crops.shape)} on {crops.device}")
+        _chk_f32(mats, (nf, 2, 3), "face_paste_affine_u8.mats", photo_u8.device)
+        S, ld = crops.shape[1], crops.shape[3]
+    _lib.check(_lib.lib().af_face_paste_affine_u8(_p(photo_u8), _p(crops) if nf else None, _p(mats) if nf else None, _p(out), H, W, nf, S, ld,
+                                                  float(erode), float(feather), _stream()), "af_face_paste_affine_u8")
     return out
 
 

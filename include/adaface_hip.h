@@ -610,6 +610,47 @@ int af_dense_conv3x3(const void* x, int ldx, int cin, const void* wt, const void
  * order), channels 3 r^2 .. cpad zero.  r in {1, 2, 4}, H % r == W % r == 0, cpad in {32, 64} and >= 3 r^2; fewer than 2^31 elements each side. */
 int af_u8_unshuffle_f16(const void* img_u8, void* out, int B, int H, int W, int r, int cpad, void* stream);
 
+/* ---- GFPGAN face restoration (adaface/gfpgan.py, GFPGANv1Clean): the kernels around the tuned convolutions.  Every argument check precedes any
+ * launch (AF_E_BADARG, the function named in af_last_error()); a tensor of 2^31 elements or more is refused (32-bit offsets).
+ *
+ * Per-sample weights of a StyleGAN2 modulated convolution, in af_gemm's packed layout.  w fp32 [cout][taps][cin] (taps 1 or 9, K = taps * cin in
+ * (ky, kx, c) order), wsq fp32 [cout][cin] = sum over the taps of w^2 (NULL allowed when demod == 0), styles fp32 [B][cin]:
+ *   d[b,o] = demod ? 1 / sqrt(sum_i styles[b,i]^2 * wsq[o,i] + 1e-8) : 1
+ *   out[(b * npad + o) * kpad + t * cin + i] = fp16(gain * d[b,o] * w[o,t,i] * styles[b,i])       for o < cout
+ * all in fp32 (the sum over i in any order), rounded to fp16 once.  Only the cout x K block of each slice is written: rows cout .. npad and
+ * columns K .. kpad are the caller's zeros, written once when the buffer is allocated.  cin % 8 == 0, kpad % 64 == 0, kpad >= K,
+ * npad % 128 == 0, npad >= cout, B * npad * kpad < 2^31, 16-byte aligned pointers. */
+int af_modulate_weights(const void* w, const void* wsq, const void* styles, void* out, int B, int cout, int cin, int taps, int npad, int kpad,
+                        int demod, float gain, void* stream);
+/* StyleConv's tail and the SFT of the next layer in one pass.  y, out fp16 [B, HW, C] (out may be y), noise fp32 [HW] (NULL allowed when
+ * nw == 0), bias fp32 [C] or NULL, scale / shift fp16 [B, HW, C / 2], both or neither:
+ *   v = y + nw * noise[p] + bias[c];  v = v >= 0 ? v : 0.2 * v;  if scale and c >= C / 2: v = v * scale[b,p,c - C/2] + shift[b,p,c - C/2]
+ *   out = fp16(min(max(v, -65504), 65504))
+ * in fp32 in this order, unfused.  The clamp makes an fp16 overflow saturate at +-65504 instead of becoming inf.  C % 8 == 0 (C % 16 == 0 with
+ * scale / shift), B * HW * C < 2^31, 16-byte aligned pointers. */
+int af_style_epilogue(const void* y, const void* noise, const void* bias, const void* scale, const void* shift, void* out, int B, int HW, int C,
+                      float nw, void* stream);
+/* x fp16 [B, H, W, C] -> out fp16 [B, 2H, 2W, C] = F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) (+ addend
+ * [B, 2H, 2W, C] or NULL).  Output row 2k reads rows (k - 1, k) with weights (0.25, 0.75), row 2k + 1 rows (k, k + 1) with (0.75, 0.25),
+ * indices clamped to [0, H - 1]; the same along x:
+ *   out = fp16(wy0 * (wx0 * x[y0,x0] + wx1 * x[y0,x1]) + wy1 * (wx0 * x[y1,x0] + wx1 * x[y1,x1]) + addend)     fp32, unfused.
+ * C % 8 == 0, B * 2H * 2W * C < 2^31, 16-byte aligned pointers, out must not overlap x. */
+int af_bilinear_up2(const void* x, const void* addend, void* out, int B, int H, int W, int C, void* stream);
+/* Restored face crops back into the photo, one launch.  photo, out uint8 [H, W, 3] (out may be photo), crops fp16 [F, S, S, ld] with RGB in
+ * channels 0-2 (nominally in [-1, 1]), mats fp32 [F, 2, 3] (image -> crop, integer pixel coordinates as in af_face_align_crop), erode >= 0 and
+ * feather >= 0 in crop pixels.  Per pixel (x, y), cur = photo[y, x] as fp32, then for f = 0 .. F - 1 in order:
+ *   (u, v) = mats[f] . (x, y, 1);  m = min(u, v, S - 1 - u, S - 1 - v);  skipped unless m > erode (alpha = 0)
+ *   t = feather > 0 ? min((m - erode) / feather, 1) : 1;  alpha = t * t * (3 - 2 t)
+ *   g = 255 * min(max(bilinear(crops[f], u, v) / 2 + 0.5, 0), 1);  cur = alpha * g + (1 - alpha) * cur        (fp32, unfused)
+ * out = rint(cur), ties to even, once at the end; a pixel no face reaches with m > erode is the photo's byte, bit for bit.  Since alpha -> 0
+ * towards the crop border, the border is never a discontinuity.  0 <= F <= 16 (F = 0: a copy; crops and mats may then be NULL), S >= 2,
+ * ld >= 3, H * W * 3 < 2^31, F * S * S * ld < 2^31. */
+int af_face_paste_affine_u8(const void* photo_u8, const void* crops, const void* mats, void* out_u8, int H, int W, int F, int S, int ld,
+                            float erode, float feather, void* stream);
+/* af_face_align_crop for the restorer's crop sizes: the same kernel and formula, size any multiple of 8 from 8 to 1024 (the recogniser's entry
+ * above keeps refusing everything but 112 and 128). */
+int af_face_align_crop_any(const void* image_u8, const void* inv_mats, void* out, int H, int W, int F, int size, void* stream);
+
 /* ---- trainable DoRA adapters on the U-Net's up_blocks.3 convolutions (adaface/diffusers_attn_lora_capture.py:541-591; peft
  * DoraConv2dLayer.forward: y = base(x) + (s - 1) * conv(xd, W) + s * scaling * B(A(xd)), xd = dropout(x)) ---------------------
  * out = y0 + u[c] * c2 + v[c] * lb   (fp16 [rows, C]; u = s - 1, v = s * scaling, fp32 [C]) */
