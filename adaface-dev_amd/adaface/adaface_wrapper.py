@@ -72,7 +72,14 @@ input limit it is a ValueError before any GPU work.  ``upscale=False`` is the ca
 before they become PIL images: every detected face is aligned, restored and pasted back with a soft border.  Without a loaded restorer or
 without a ``vae`` it is a ValueError before any GPU work.  ``restore_faces=False`` is the call as it was.
 
-SDXL / SD3 / flux pipelines, LCM-distilled U-Nets, schedulers other than DDIM, DPM-Solver++ and LCM, U-Net ensembles and the
+``forward(..., control_image=img, control_scale=1.0, control_guidance_start=0.0, control_guidance_end=1.0)`` (INTEGRATION.md
+"ControlNet") steers all three pipelines, under all three samplers and with ``num_frames``, with a ControlNet (``controlnet=`` at
+construction or ``load_controlnet``: a ``ControlNet`` or a local cldm-layout file / state dict;
+ldm/modules/diffusionmodules/controlnet.py).  ``control_image`` is a PIL image, a uint8 tensor ``[H, W, 3]`` / ``[B, H, W, 3]`` or a list,
+1 image (shared) or one per sampled row, exactly 8 x the latent size.  The hints are encoded once, the ControlNet sits on the U-Net during
+the sampling call only, and the sampler's per-step callback switches it by the guidance window.  Without ``control_image`` every path is
+the call as it was.
+
 ``forward(photo, ..., mask_image="face", crop_padding=0.5)`` (``inpaint`` only; INTEGRATION.md "Repainting faces in a photo") repaints
 the faces of ONE photo of any size (a PIL image, a path or a uint8 array) and hands back the same photo: ``face_detector`` (any callable
 with ``FaceIDExtractor``'s detector contract, e.g. a ``RetinaFaceDetector``; by default the ``face_id_extractor``'s) finds the faces,
@@ -155,6 +162,30 @@ def inpaint_masks(mask_images, out_image_count, size):
     return torch.from_numpy(np.stack(out)[:, None].astype(np.float32))
 
 
+def control_images_u8(control_image, rows):
+    """ControlNet input preparation on the host: a PIL image, a uint8 tensor [H, W, 3] / [B, H, W, 3] or a list of either, 1 (shared by all
+    rows) or ``rows`` of them, all of one size.  Nothing is resized.  Returns uint8 [B_ctl, H, W, 3] (on the device the tensors were on)."""
+    from PIL import Image
+    items = list(control_image) if isinstance(control_image, (list, tuple)) else [control_image]
+    out = []
+    for im in items:
+        if isinstance(im, Image.Image):
+            out.append(torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.uint8).copy()))
+        elif torch.is_tensor(im) and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3:
+            out.append(im)
+        elif torch.is_tensor(im) and im.dtype == torch.uint8 and im.dim() == 4 and im.shape[3] == 3:
+            out.extend(im)
+        else:
+            raise ValueError("control_image must be a PIL image, a uint8 tensor [H, W, 3] / [B, H, W, 3] or a list of them, got "
+                             f"{(im.dtype, tuple(im.shape)) if torch.is_tensor(im) else type(im).__name__}")
+    if len(out) not in (1, rows):
+        raise ValueError(f"control_image: 1 image (shared) or one per sampled row ({rows}) expected, got {len(out)}")
+    sizes = {tuple(t.shape[:2]) for t in out}
+    if len(sizes) != 1:
+        raise ValueError(f"control images must all have the same size, got {sorted(sizes)}")
+    return torch.stack(out)
+
+
 MAX_IMAGE_SIDE = 1024      # pixels; the VAE (its fused attention layer, 16384 tokens) is built and tested up to a 128 x 128 latent
 
 
@@ -230,7 +261,7 @@ class AdaFaceWrapper(nn.Module):
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
                  lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None, face_detector=None, motion_module_path=None,
-                 beta_schedule="linear", upscaler=None, face_restorer=None):
+                 beta_schedule="linear", upscaler=None, face_restorer=None, controlnet=None):
         super().__init__()
         if pipeline_name not in ("text2img", "img2img", "inpaint", None):
             raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img, img2img and inpaint paths (and None = face "
@@ -288,6 +319,7 @@ class AdaFaceWrapper(nn.Module):
         self.__dict__["upscaler"] = None          # an esrgan.Upscaler (load_upscaler) for forward(upscale=True); not a submodule
         self.__dict__["face_restorer"] = None     # a gfpgan.FaceRestorer (load_face_restorer) for forward(restore_faces=True); not a submodule
         self.__dict__["motion_module"] = None     # a MotionModule (load_motion_module); not a submodule: it is on the U-Net only inside forward(num_frames=F)
+        self.__dict__["controlnet"] = None        # a ControlNet (load_controlnet); not a submodule: it is on the U-Net only inside forward(control_image=...)
         self.vae = vae
         self.img_prompt_embs = None
         self._lcm_lora = None                 # (read_unet_lora dict, scale) of the fused LoRA
@@ -305,6 +337,8 @@ class AdaFaceWrapper(nn.Module):
             self.load_upscaler(upscaler)
         if face_restorer is not None:
             self.load_face_restorer(face_restorer)
+        if controlnet is not None:
+            self.load_controlnet(controlnet)
 
     # ------------------------------------------------------------------ checkpoints
     def load_base_model(self, base_model_path):
@@ -344,6 +378,77 @@ class AdaFaceWrapper(nn.Module):
         self.__dict__["motion_module"] = None
         if self.ldm is not None:
             self.ldm.model.diffusion_model.set_motion(None)
+
+    def load_controlnet(self, path_or_net):
+        """A ControlNet for ``forward(..., control_image=...)`` (ldm/modules/diffusionmodules/controlnet.py; INTEGRATION.md "ControlNet"): a
+        ``ControlNet``, or a local cldm-layout ``.pth`` / ``.ckpt`` / ``.safetensors`` file or its state dict, loaded strictly for this
+        wrapper's U-Net.  Nothing is downloaded."""
+        from ..ldm.modules.diffusionmodules.controlnet import ControlNet, load_controlnet
+        if self.ldm is None:
+            raise RuntimeError("pipeline_name=None builds the face encoder only: there is no U-Net to put a ControlNet on")
+        unet = self.ldm.model.diffusion_model
+        cn = path_or_net
+        if not isinstance(cn, ControlNet):
+            cfg = dict(in_channels=unet.in_channels, model_channels=unet.model_channels, num_res_blocks=unet.num_res_blocks,
+                       attention_resolutions=unet.attention_resolutions, channel_mult=unet.channel_mult, num_heads=unet.num_heads,
+                       num_head_channels=unet.num_head_channels, use_spatial_transformer=True,
+                       context_dim=unet._cross_attn_layers()[0].to_k.in_features)
+            cn = load_controlnet(cn, cfg)
+        probe = torch.zeros((1, 1, 1, unet.model_channels), dtype=torch.float16)
+        unet.set_control(cn, probe)                              # refuses widths or a topology that do not match this U-Net
+        unet.set_control(None)
+        self.__dict__["controlnet"] = cn
+        return cn
+
+    def unload_controlnet(self):
+        self.__dict__["controlnet"] = None
+        if self.ldm is not None:
+            self.ldm.model.diffusion_model.set_control(None)
+
+    def _check_control(self, control_image, control_scale, start, end, rows, hires_size, repaint):
+        """The refusals of forward(control_image=...) that need no image size (INTEGRATION.md "ControlNet"), all before any GPU work.  Returns
+        the control images as uint8 [1 | rows, H, W, 3]."""
+        if self.controlnet is None:
+            raise ValueError("control_image is given but no ControlNet is loaded (controlnet= at construction / load_controlnet)")
+        if hires_size is not None:
+            raise ValueError("control_image together with hires_size: the second pass runs at another size and resampling hints is not built")
+        if repaint is not None:
+            raise ValueError("control_image together with mask_image='face' or crop_padding: the working size is chosen under the hint and "
+                             "resampling hints is not built")
+        if isinstance(control_scale, bool) or not isinstance(control_scale, (int, float)) or not np.isfinite(control_scale):
+            raise ValueError(f"control_scale must be a finite number, got {control_scale!r}")
+        ok = all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (start, end))
+        if not ok or not 0 <= start < end <= 1:
+            raise ValueError(f"the control guidance window needs 0 <= control_guidance_start < control_guidance_end <= 1, got {start!r}, {end!r}")
+        return control_images_u8(control_image, rows)
+
+    @staticmethod
+    def _check_control_size(images, latent_hw):
+        if tuple(images.shape[1:3]) != (8 * latent_hw[0], 8 * latent_hw[1]):
+            raise ValueError(f"control images must be exactly 8 x the latent size, {8 * latent_hw[1]} x {8 * latent_hw[0]} pixels, got "
+                             f"{images.shape[2]} x {images.shape[1]} (nothing is resized)")
+
+    def _sample_controlled(self, control, n_steps, call):
+        """``call(**kw)`` runs one of the sampler's loops.  With ``control`` = (images uint8, scale, start, end) the ControlNet is on the
+        U-Net around that call only: the hints are encoded once, and the sampler's per-step callback switches the control off and on by the
+        guidance window (active at step i of n iff i / n >= start and (i + 1) / n <= end).  Without it this is ``call()``: the sampler is
+        called exactly as before."""
+        if control is None:
+            return call()
+        from ..ldm.modules.diffusionmodules.controlnet import guidance_window_active
+        images, scale, start, end = control
+        unet = self.ldm.model.diffusion_model
+        cn = self.controlnet.to(self.device)
+        unet.set_control(cn, cn.hint_features(images.to(self.device)), scale)
+
+        def switch(i):
+            unet.set_control_active(i < n_steps and guidance_window_active(i, n_steps, start, end))
+
+        try:
+            switch(0)
+            return call(callback=lambda i: switch(i + 1))                # the callback runs behind step i
+        finally:
+            unet.set_control(None)
 
     def load_upscaler(self, path_or_net):
         """A Real-ESRGAN upscaler for ``forward(..., upscale=True)`` (adaface/esrgan.py; INTEGRATION.md "Upscaling (Real-ESRGAN)"): an
@@ -565,7 +670,8 @@ class AdaFaceWrapper(nn.Module):
                 ablate_prompt_no_placeholders=False, ablate_prompt_embed_type="ada", nonmix_prompt_emb_weight=0,
                 repeat_prompt_for_each_encoder=True, verbose=False, mask_image=None, hires_size=None, hires_strength=0.7,
                 hires_steps=None, hires_upscaler="bilinear", crop_padding=None, face_index=None, face_mask_expand=1.3,
-                face_mask_feather=0.25, work_size=None, num_frames=None, upscale=False, restore_faces=False):
+                face_mask_feather=0.25, work_size=None, num_frames=None, upscale=False, restore_faces=False, control_image=None,
+                control_scale=1.0, control_guidance_start=0.0, control_guidance_end=1.0):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
         if upscale:
@@ -577,6 +683,10 @@ class AdaFaceWrapper(nn.Module):
             videos = out_image_count
             out_image_count = videos * num_frames          # the batch is video-major: row v * F + f, the prompt repeated per frame
         repaint = self._check_repaint(noise, mask_image, crop_padding, face_index, face_mask_expand, face_mask_feather, work_size)
+        control = None
+        if control_image is not None:
+            control = (self._check_control(control_image, control_scale, control_guidance_start, control_guidance_end, out_image_count,
+                                           hires_size, repaint), float(control_scale), control_guidance_start, control_guidance_end)
         if hires_size is not None:
             hires_hw, hires_steps = self._check_hires(hires_size, hires_strength, hires_steps, hires_upscaler)
         if upscale and self.pipeline_name == "text2img":
@@ -607,9 +717,15 @@ class AdaFaceWrapper(nn.Module):
             if inpaint and repaint is None:
                 masks = inpaint_masks(mask_image, out_image_count, (images_u8.shape[2], images_u8.shape[1]))
             self._sampler().img2img_steps(self.num_inference_steps, ref_img_strength)    # refuse a bad strength before any work
+            if control is not None:
+                self._check_control_size(control[0], (images_u8.shape[1] // 8, images_u8.shape[2] // 8))
         elif self.vae is not None and torch.is_tensor(noise) and noise.dim() == 4 and max(noise.shape[2:]) * 8 > MAX_IMAGE_SIDE:
             raise ValueError(f"text2img latents may be at most {MAX_IMAGE_SIDE // 8} on a side ({MAX_IMAGE_SIDE} pixels, the VAE's limit), got "
                              f"noise of shape {tuple(noise.shape)}")
+        if control is not None and self.pipeline_name == "text2img":
+            if not torch.is_tensor(noise) or noise.dim() != 4:
+                raise ValueError("control_image needs noise [rows, 4, h, w] to take the latent size from")
+            self._check_control_size(control[0], tuple(noise.shape[2:]))
         if prompt_embeds is None:
             pe, ne, _, _ = self.encode_prompt(prompt, negative_prompt, placeholder_tokens_pos=placeholder_tokens_pos,
                                               ablate_prompt_only_placeholders=ablate_prompt_only_placeholders,
@@ -628,14 +744,15 @@ class AdaFaceWrapper(nn.Module):
         cond = (pe, [prompt or ""] * out_image_count, {})
         uncond = None if ne is None else (ne, [negative_prompt or self.negative_prompt] * out_image_count, {})
         if self.pipeline_name == "img2img":
-            _, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
+            n_run, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
             x_t = self.ldm.img2img_latents(images_u8.to(self.device), out_image_count, t_first, generator=generator,
                                            first_stage_model=self.vae)
-            latents, _ = sampler.sample_img2img(self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond,
-                                                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
+            latents, _ = self._sample_controlled(control, n_run, lambda **cb: sampler.sample_img2img(
+                self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond, guidance_scale=guidance_scale,
+                unconditional_conditioning=uncond, generator=generator, **cb))
             return self._to_pil(latents, upscale, restore_faces)
         if inpaint:
-            _, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
+            n_run, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
             if repaint is not None:
                 photo = torch.from_numpy(repaint["photo"]).to(self.device)
                 if repaint["ellipses"] is not None:
@@ -645,9 +762,9 @@ class AdaFaceWrapper(nn.Module):
                 images_u8, masks = ops.crop_resize_u8(photo, alpha, repaint["rect"], repaint["work_hw"], 1.0 / 255.0)
             x_start, z, n_fwd = self.ldm.inpaint_latents(images_u8.to(self.device), out_image_count, t_first, generator=generator,
                                                          first_stage_model=self.vae, from_noise=ref_img_strength == 1)
-            latents, _ = sampler.sample_inpaint(self.num_inference_steps, ref_img_strength, out_image_count, x_start, z, n_fwd,
-                                                masks.to(self.device), cond, guidance_scale=guidance_scale,
-                                                unconditional_conditioning=uncond, generator=generator)
+            latents, _ = self._sample_controlled(control, n_run, lambda **cb: sampler.sample_inpaint(
+                self.num_inference_steps, ref_img_strength, out_image_count, x_start, z, n_fwd, masks.to(self.device), cond,
+                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb))
             if repaint is not None:
                 return self._paste_back(latents, photo, alpha, repaint["rect"], upscale, restore_faces)
             return self._to_pil(latents, upscale, restore_faces)
@@ -657,8 +774,10 @@ class AdaFaceWrapper(nn.Module):
             self.motion_module.to(self.device)
             unet.set_motion(self.motion_module, num_frames)           # around the sampling call only
         try:
-            latents, _ = sampler.sample(self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise,
-                                        verbose=False, guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator)
+            n_run = len(sampler.timesteps(self.num_inference_steps)) if control is not None else None
+            latents, _ = self._sample_controlled(control, n_run, lambda **cb: sampler.sample(
+                self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise, verbose=False,
+                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb))
         finally:
             if num_frames is not None:
                 unet.set_motion(None)

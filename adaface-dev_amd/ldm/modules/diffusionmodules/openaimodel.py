@@ -388,14 +388,8 @@ class UNetModel(nn.Module):
             normalization(ch), nn.SiLU(), zero_module(conv_nd(dims, model_channels, out_channels, 3, padding=1))
         )
 
-        # batched emb_layers projection: slices assigned in module order
-        self._resblocks = [m for m in self.modules() if isinstance(m, ResBlock)]
-        off = 0
-        for rb in self._resblocks:
-            rb._emb_slice = (off, rb.out_channels)
-            off += ops.round_up(rb.out_channels, 8)
-        self._emb_total = off
-        self._emb_cache = _PackCache()
+        self._assign_emb_slices()
+        self.__dict__["_control"] = None         # set_control's state ({"net", "hint", "scale", "expanded", "active"}) while it holds a ControlNet; not a submodule either
         self.__dict__["_motion"] = None          # (MotionModule, num_frames) while set_motion holds one; not a submodule: the state dict stays SD-1.5's
 
     # ------------------------------------------------------------------ reference flag plumbing
@@ -443,6 +437,16 @@ class UNetModel(nn.Module):
         return apply(ca_flag_dict, ca_idx, "ca"), apply(trans_flag_dict, tr_idx, "trans")
 
     # ------------------------------------------------------------------ packing
+    def _assign_emb_slices(self):
+        """The batched emb_layers projection: slices assigned in module order."""
+        self._resblocks = [m for m in self.modules() if isinstance(m, ResBlock)]
+        off = 0
+        for rb in self._resblocks:
+            rb._emb_slice = (off, rb.out_channels)
+            off += ops.round_up(rb.out_channels, 8)
+        self._emb_total = off
+        self._emb_cache = _PackCache()
+
     def _packed_emb_all(self):
         params = []
         for rb in self._resblocks:
@@ -496,6 +500,63 @@ class UNetModel(nn.Module):
         if self._motion is not None:
             raise NotImplementedError(f"{what} is not built for video: unset the motion module (set_motion(None)) first")
 
+    # ------------------------------------------------------------------ ControlNet (ldm/modules/diffusionmodules/controlnet.py)
+    def set_control(self, controlnet, hint_features=None, scale=1.0):
+        """Run ``controlnet`` (a ControlNet) inside ``hip``: after this U-Net's input blocks the ControlNet walks the same latents and adds
+        ``scale`` x its thirteen zero-convolution outputs to the twelve skips and to the middle block's output, each join in the epilogue of
+        the zero convolution's GEMM.  ``hint_features``: ``controlnet.hint_features(images)``, fp16 [B0, h, w, model_channels]; row b of a
+        batch takes hint b % B0.  ``None`` restores the plain walk exactly.  Refuses (ValueError) a ControlNet whose widths or topology do
+        not match this U-Net, and, when run, a batch that is not a multiple of B0 or latents of another size than the hints."""
+        if controlnet is None:
+            self.__dict__["_control"] = None
+            return
+        for name in ("in_channels", "model_channels", "num_res_blocks", "num_heads", "num_head_channels"):
+            if getattr(controlnet, name) != getattr(self, name):
+                raise ValueError(f"set_control: the ControlNet's {name} is {getattr(controlnet, name)}, the U-Net's {getattr(self, name)}")
+        for name in ("channel_mult", "attention_resolutions"):
+            if list(getattr(controlnet, name)) != list(getattr(self, name)):
+                raise ValueError(f"set_control: the ControlNet's {name} is {list(getattr(controlnet, name))}, the U-Net's {list(getattr(self, name))}")
+        if len(controlnet.input_blocks) != len(self.input_blocks) or len(controlnet.zero_convs) != len(self.input_blocks):
+            raise ValueError(f"set_control: the ControlNet has {len(controlnet.input_blocks)} input blocks, the U-Net {len(self.input_blocks)}")
+        for n, (a, b) in enumerate(zip(controlnet.input_blocks, self.input_blocks)):
+            if [type(m) for m in a] != [type(m) for m in b]:
+                raise ValueError(f"set_control: input block {n} of the ControlNet does not have the U-Net's layers")
+        cn_ctx, own_ctx = controlnet._cross_attn_layers(), self._cross_attn_layers()
+        if cn_ctx and own_ctx and cn_ctx[0].to_k.in_features != own_ctx[0].to_k.in_features:
+            raise ValueError(f"set_control: the ControlNet's context_dim is {cn_ctx[0].to_k.in_features}, the U-Net's {own_ctx[0].to_k.in_features}")
+        h = hint_features
+        if not torch.is_tensor(h) or h.dtype != F16 or h.dim() != 4 or h.shape[0] < 1 or h.shape[3] != self.model_channels:
+            raise ValueError(f"set_control: hint_features must be fp16 [B0, h, w, {self.model_channels}] (ControlNet.hint_features), got "
+                             f"{(h.dtype, tuple(h.shape)) if torch.is_tensor(h) else type(h).__name__}")
+        scale = float(scale)
+        if scale != scale or scale in (float("inf"), float("-inf")):
+            raise ValueError(f"set_control: scale must be finite, got {scale}")
+        self.__dict__["_control"] = {"net": controlnet, "hint": h.contiguous(), "scale": scale, "expanded": {}, "active": True}
+
+    def set_control_active(self, active):
+        """Switch the ControlNet that is set off or on between two steps (a guidance window) without dropping its expanded hints; while it
+        is off, ``hip`` is the plain walk.  Everything ``_refuse_control`` refuses stays refused until ``set_control(None)``."""
+        if self._control is None:
+            raise ValueError("set_control_active: no ControlNet is set")
+        self._control["active"] = bool(active)
+
+    def _refuse_control(self, what):
+        if self._control is not None:
+            raise NotImplementedError(f"{what} is not built with a ControlNet: unset it (set_control(None)) first")
+
+    def _control_hint(self, B, hw):
+        """The hint features for a batch of B rows (row b: hint b % B0), expanded once per batch size and kept."""
+        ctrl = self._control
+        hint = ctrl["hint"]
+        B0 = hint.shape[0]
+        if B % B0:
+            raise ValueError(f"the batch ({B}) is not a multiple of the hint batch ({B0})")
+        if tuple(hint.shape[1:3]) != tuple(hw):
+            raise ValueError(f"the hints are for {hint.shape[1]} x {hint.shape[2]} latents, the batch holds {hw[0]} x {hw[1]}")
+        if B not in ctrl["expanded"]:
+            ctrl["expanded"][B] = hint if B == B0 else hint.repeat(B // B0, 1, 1, 1)
+        return ctrl["expanded"][B]
+
     def _hip_block_motion(self, module, where, n, h, emb, context, img_mask):
         """``module.hip`` with the temporal transformer placed at (where, n), if any: behind an input block, between the middle block's
         SpatialTransformer and its second ResBlock, in front of an output block's Upsample."""
@@ -524,7 +585,7 @@ class UNetModel(nn.Module):
         emb = self._embed(timesteps)   # SiLU(emb) (its only consumers are the emb_layers) + all 22 projections
         kv_layers = self._project_context_all(context)
         try:
-            return self._hip_blocks(x_nhwc, emb, context, img_mask, capture_layers)
+            return self._hip_blocks(x_nhwc, emb, context, img_mask, capture_layers, timesteps)
         finally:
             for m in kv_layers:
                 m._kv_pre = None
@@ -560,7 +621,7 @@ class UNetModel(nn.Module):
             off += c
         return layers
 
-    def _hip_blocks(self, x_nhwc, emb, context, img_mask, capture_layers):
+    def _hip_blocks(self, x_nhwc, emb, context, img_mask, capture_layers, timesteps=None):
         acts = {}
         hs = []
         h = x_nhwc
@@ -589,7 +650,15 @@ class UNetModel(nn.Module):
             if layer_idx in capture_layers:
                 collect(module, h)
             layer_idx += 1
+        ctrl = self._control if self._control is not None and self._control["active"] else None
+        if ctrl is not None:
+            # the ControlNet walks the same latents (per frame, without temporal layers, when a motion module is set too) and hands back the
+            # joined skips as fresh tensors; the middle residual is joined behind this U-Net's middle block
+            hint = self._control_hint(x_nhwc.shape[0], x_nhwc.shape[1:3])
+            hs, mid = ctrl["net"].hip_walk(x_nhwc, timesteps, context, hint, hs, ctrl["scale"], img_mask)
         h = run(self.middle_block, "middle", 1, h)
+        if ctrl is not None:
+            h = ctrl["net"].join_middle(mid, h, ctrl["scale"])
         if layer_idx in capture_layers:
             collect(self.middle_block, h)
         layer_idx += 1
@@ -606,6 +675,7 @@ class UNetModel(nn.Module):
         (a step's shared gradient-free trunk, LatentDiffusion.guided_denoise): -> (eps NHWC, captured activations) exactly as ``_hip_blocks``
         leaves them for those layers."""
         self._refuse_motion("the trunk cache (hip_tail)")
+        self._refuse_control("the trunk cache (hip_tail)")
         h, skips = trunk
         emb = self._embed(timesteps)
         kv_layers = self._project_context_all(context)
@@ -637,6 +707,7 @@ class UNetModel(nn.Module):
     def hip_train(self, x_nhwc, timesteps, context, img_mask=None):
         """Forward that keeps the activations the backward needs.  -> (eps [B,H,W,out_channels], saved)."""
         self._refuse_motion("hip_train")
+        self._refuse_control("hip_train")
         emb = self._embed(timesteps)
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
@@ -655,6 +726,7 @@ class UNetModel(nn.Module):
         """hip_train without the last ``n_tail`` decoder blocks and the output head (modules/diffusionmodules/capture_graph.py):
         -> (h, [the skips those blocks will pop, in pop order], saved)."""
         self._refuse_motion("hip_train_trunk")
+        self._refuse_control("hip_train_trunk")
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
         for module in self.input_blocks:
@@ -674,6 +746,7 @@ class UNetModel(nn.Module):
         input and context carry none): the inference walk -- every cross-attention layer's k / v from one GEMM, the fused C = 320 blocks,
         nothing saved -- up to the last ``n_tail`` decoder blocks.  -> (h, [the skips those blocks pop, in pop order])."""
         self._refuse_motion("the trunk cache (hip_trunk)")
+        self._refuse_control("the trunk cache (hip_trunk)")
         kv_layers = self._project_context_all(context)
         try:
             hs = []
@@ -758,6 +831,7 @@ class UNetModel(nn.Module):
             # attention LoRAs) as a chain of autograd nodes -- modules/diffusionmodules/capture_graph.py
             from .capture_graph import unet_forward_captured
             self._refuse_motion("the captured / score-rewrite path")
+            self._refuse_control("the captured / score-rewrite path")
             if extra_info is None:
                 raise ValueError("extra_info must be a dict on the capture / score-rewrite path")
             if capture:
@@ -768,6 +842,7 @@ class UNetModel(nn.Module):
             return eps
         if trainable:
             self._refuse_motion("training")
+            self._refuse_control("training")
             gs = float((extra_info or {}).get("res_hidden_states_gradscale", 1) or 1)
             lora = (extra_info or {}).get("_ffn_lora_adapters")           # set by UNetWrapper when use_ffn_lora is on
             return _UNetFunction.apply(self, x, timesteps, context, img_mask, gs, lora, *[t[3] for t in lora_param_order(lora)])

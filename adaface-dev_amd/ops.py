@@ -1743,6 +1743,39 @@ def u8_unshuffle_f16(img_u8: torch.Tensor, r: int, cpad: int) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------- ControlNet (ldm/modules/diffusionmodules/controlnet.py)
+def pack_hint_conv3x3(weight: torch.Tensor) -> torch.Tensor:
+    """A torch conv weight [cout, cin, 3, 3] -> af_hint_conv3x3's fp16 [cout][9 * cpad] (K order (ky, kx, c)), input channels zero-padded to
+    cpad = cin rounded up to a multiple of 32 (include/adaface_hip.h)."""
+    cout, cin = weight.shape[:2]
+    cp = (cin + 31) // 32 * 32
+    w = torch.zeros((cout, 3, 3, cp), dtype=F16, device=weight.device)
+    w[:, :, :, :cin] = weight.detach().permute(0, 2, 3, 1).to(F16)
+    return w.reshape(cout, 9 * cp).contiguous()
+
+
+def hint_conv3x3(x: torch.Tensor, wt: torch.Tensor, bias: Optional[torch.Tensor], *, stride: int = 1, act: bool = True) -> torch.Tensor:
+    """One af_hint_conv3x3 launch: 3x3 / pad 1 / stride 1 | 2 convolution of x -- fp16 NHWC [B, H, W, cin], or a uint8 RGB image [B, H, W, 3]
+    read as x / 255 -- with ``wt`` as pack_hint_conv3x3 makes it and ``bias`` fp32 [cout] or None -> fp16 [B, Ho, Wo, cout], SiLU under ``act``."""
+    if x.dtype not in (F16, torch.uint8) or not x.is_cuda or not x.is_contiguous() or x.dim() != 4 or x.numel() == 0:
+        raise RuntimeError(f"hint_conv3x3: expected a non-empty contiguous fp16 or uint8 device tensor [B, H, W, C], got {x.dtype} "
+                           f"{tuple(x.shape)} on {x.device}")
+    B, H, W, cin = x.shape
+    mode = int(x.dtype == torch.uint8)
+    cp = (cin + 31) // 32 * 32
+    if wt.dtype != F16 or not wt.is_cuda or not wt.is_contiguous() or wt.dim() != 2 or wt.shape[1] != 9 * cp:
+        raise RuntimeError(f"hint_conv3x3: wt must be a contiguous fp16 device tensor [cout, {9 * cp}] (pack_hint_conv3x3), got {wt.dtype} "
+                           f"{tuple(wt.shape)} on {wt.device}")
+    cout = wt.shape[0]
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_cuda or not bias.is_contiguous() or tuple(bias.shape) != (cout,)):
+        raise RuntimeError(f"hint_conv3x3: bias must be a contiguous fp32 device tensor [{cout}], got {bias.dtype} {tuple(bias.shape)}")
+    s = int(stride)
+    out = torch.empty((B, (H - 1) // max(s, 1) + 1, (W - 1) // max(s, 1) + 1, cout), dtype=F16, device=x.device)
+    _lib.check(_lib.lib().af_hint_conv3x3(_p(x), mode, cin, _p(wt), _p(bias), _p(out), cout, s, int(bool(act)), B, H, W, _stream()),
+               "af_hint_conv3x3")
+    return out
+
+
 # ----------------------------------------------------------------------------- profiling hook
 def prof_enable(on: bool):
     _lib.check(_lib.lib().af_prof_enable(int(on)), "af_prof_enable")

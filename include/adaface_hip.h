@@ -651,6 +651,26 @@ int af_face_paste_affine_u8(const void* photo_u8, const void* crops, const void*
  * above keeps refusing everything but 112 and 128). */
 int af_face_align_crop_any(const void* image_u8, const void* inv_mats, void* out, int H, int W, int F, int size, void* stream);
 
+/* ---- ControlNet (ldm/modules/diffusionmodules/controlnet.py): the hint encoder's convolution.  A 3x3 convolution, pad 1, stride s in {1, 2},
+ * for the narrow channel counts the tuned 128-column tiles idle on, with bias and SiLU in the epilogue:
+ *   y[b,i,j,n] = bias[n] + sum_{ky,kx,c<cin} w[n][ky][kx][c] * X[b, s*i+ky-1, s*j+kx-1, c]        (zero outside the image, fp32 accumulation)
+ *   out[b,i,j,n] = fp16(act ? y * sigmoid(y) : y)      Ho = (H-1)/s + 1, Wo = (W-1)/s + 1, out fp16 NHWC [B,Ho,Wo,cout] tight
+ * in_mode 0: x fp16 NHWC [B,H,W,cin] tight, cin % 16 == 0, 16 <= cin <= 256, X = x.
+ * in_mode 1: x uint8 [B,H,W,3], cin = 3, X = x / 255: the bytes enter the products as the exact integers 0 .. 255 and the 1 / 255 multiplies
+ *            the fp32 sum (no fp16 copy of the image exists, in memory or in rounding).
+ * cout % 16 == 0, 16 <= cout <= 256.  bias fp32 [cout] or NULL (no bias).  act in {0, 1}.
+ * Device weight layout: wt fp16 [cout][9 * cpad], cpad = cin rounded up to a multiple of 32 (3 -> 32, 16 -> 32, 96 -> 96, 256 -> 256),
+ *   wt[n * 9 * cpad + (ky * 3 + kx) * cpad + c] = fp16(w[n][ky][kx][c]) for c < cin and ZERO for cin <= c < cpad.
+ *   The zero rows are part of the contract: the kernel multiplies them with the zeros it supplies for the missing channels.
+ * x (in_mode 0) and wt 16-byte aligned, out 8-byte, bias 4-byte.  out must not overlap x, wt or bias (the caller's duty, not checked).
+ * One launch, no workspace, on `stream`.  Exactly B*Ho*Wo*cout elements of out are written; nothing outside x's B*H*W*cin elements, wt's
+ * cout*9*cpad and bias's cout is read: the zero border comes from predication, not from a padded copy.
+ * AF_E_BADARG before any launch (af_last_error() names the function): NULL x / wt / out, B, H or W below 1, in_mode outside {0, 1}, cin or cout
+ * outside the above, a stride other than 1 or 2, act outside {0, 1}, a misaligned pointer, B*H*W*cin or B*Ho*Wo*cout at or above 2^31
+ * (32-bit offsets), more than 65535 patch rows (Ho / 16 at stride 1, Ho / 8 at stride 2) or B times the number of channel slabs (at most cout / 16) above 65535. */
+int af_hint_conv3x3(const void* x, int in_mode, int cin, const void* wt, const void* bias, void* out, int cout, int stride, int act, int B,
+                    int H, int W, void* stream);
+
 /* ---- trainable DoRA adapters on the U-Net's up_blocks.3 convolutions (adaface/diffusers_attn_lora_capture.py:541-591; peft
  * DoraConv2dLayer.forward: y = base(x) + (s - 1) * conv(xd, W) + s * scaling * B(A(xd)), xd = dropout(x)) ---------------------
  * out = y0 + u[c] * c2 + v[c] * lb   (fp16 [rows, C]; u = s - 1, v = s * scaling, fp32 [C]) */
