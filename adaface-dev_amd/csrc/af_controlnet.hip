@@ -2,26 +2,15 @@
 //   af_hint_conv3x3      3x3 convolution (pad 1, stride 1 or 2) for narrow channel counts (16 .. 256 in, 16 .. 256 out, or a uint8 RGB image in):
 //                        bias and SiLU in the epilogue, fp16 NHWC out.
 //
-// The tuned implicit-GEMM tiles are 128 columns wide and idle on N = 16 / 32 / 96; af_dense_conv3x3 (af_esrgan.hip) has the right shape of tile
-// but neither stride 2 nor these channel ranges.  This kernel keeps its frame: an implicit GEMM on v_mfma_f32_16x16x32_f16 whose A operand is
-// the WEIGHTS (row = output channel) and whose B operand the PIXELS (column = the 16 pixels of one output row of the patch), so a lane ends up
-// with four consecutive channels of one pixel: 8-byte stores.  A workgroup of four waves owns a patch of output pixels of one image -- 16 x 16
-// at stride 1 (wave w: rows 4 w .. 4 w + 3), 8 x 16 at stride 2 (wave w: rows 2 w, 2 w + 1) -- and a slab of NT <= 4 fragments (16 NT channels)
-// of cout; blockIdx.z runs over images x slabs.  Per 32-channel chunk of the input the patch's halo (18 x 18 input pixels at stride 1, 17 x 33
-// at stride 2) goes into LDS once and the nine taps read it at shifted addresses.  Halo pixels outside the image, and channels behind cin in
-// the last chunk, are written as zeros by predication and never read from memory.
-// LDS image: four planes, one per 16-byte (8-channel) piece of the chunk, each [halo pixels][16 bytes], plane stride a multiple of the 256-byte
-// bank row.  At stride 2 a halo row is stored de-interleaved (even columns 0 .. 16, then odd columns 17 .. 32), so the sixteen pixels 2 j + kx
-// of a B fragment sit in sixteen consecutive 16-byte slots exactly as at stride 1: conflict-free ds_read_b128 at both strides.
-// in_mode 1 (uint8 RGB image): the three bytes of a pixel are put into the halo as the exact fp16 integers 0 .. 255 (channels 3 .. 31 zero) and
-// the 1 / 255 is applied to the fp32 accumulator, so the image is neither copied to fp16 in memory nor rounded.
-// Weights ([cout][9 cpad] halves, at most 1.2 MB, L2-resident) come straight from global memory as K-contiguous 16-byte fragments, one tap ahead
-// of the MFMAs that use them (a whole chunk ahead where NT <= 2 leaves the registers for it).
-#include "af_common.h"
+// It runs on the patch frame of af_conv3x3_patch.h at both strides: a workgroup owns a patch of output pixels of one image and a slab of
+// NT <= 4 fragments (16 NT channels) of cout; blockIdx.z runs over images x slabs.  This file has what is the hint kernel's own.  Its source of
+// halo pixels is a cin-dense NHWC tensor with bounds on the INPUT grid, whose channels behind cin in the last chunk are zeros by predication and
+// never read from memory; or, at in_mode 1, a uint8 RGB image: the three bytes of a pixel are put into the halo as the exact fp16 integers
+// 0 .. 255 (channels 3 .. 31 zero) and the 1 / 255 is applied to the fp32 accumulator, so the image is neither copied to fp16 in memory nor
+// rounded.  Its weights are [cout][9 cpad] halves (at most 1.2 MB).  Its epilogue writes whole fragments (cout % 16 == 0).
+#include "af_conv3x3_patch.h"
 
 namespace {
-
-constexpr long LIM = 1L << 31;
 
 struct HintArgs {
   const void* x;
@@ -30,125 +19,40 @@ struct HintArgs {
   half_t* out;
   int in_mode, cin, cpad, cout, act, nslab, H, W, Ho, Wo;
   float scale;
+
+  // the frame's Src: index of the input pixel
+  __device__ int locate(int b, int y, int x_, int) const { return y >= 0 && y < H && x_ >= 0 && x_ < W ? (b * H + y) * W + x_ : -1; }
+  __device__ uintx4_t fetch(int h, int c0, int q) const {
+    uintx4_t v = {0u, 0u, 0u, 0u};
+    if (in_mode == 0) {
+      if (c0 + q * 8 < cin) v = *reinterpret_cast<const uintx4_t*>((const half_t*)x + h * cin + c0 + q * 8);
+    } else if (q == 0) {
+      const unsigned char* p = (const unsigned char*)x + h * 3;
+      const half8_t px = {(half_t)(float)p[0], (half_t)(float)p[1], (half_t)(float)p[2], (half_t)0.f,
+                          (half_t)0.f,         (half_t)0.f,         (half_t)0.f,         (half_t)0.f};
+      v = __builtin_bit_cast(uintx4_t, px);
+    }
+    return v;
+  }
 };
 
 template <int S, int NT>
 __global__ __launch_bounds__(256) void hint_conv3x3_kernel(const HintArgs a) {
-  constexpr int PR = S == 1 ? 4 : 2;                     // output rows per wave
-  constexpr int TY = 4 * PR;                             // output rows per workgroup
-  constexpr int HH = S * (TY - 1) + 3, HW = S * 15 + 3;  // halo: 18 x 18 | 17 x 33 input pixels
-  constexpr int HPIX = HH * HW;
-  constexpr int PLANE = (HPIX * 16 + 255) / 256 * 256;   // 5376 | 9216 bytes
-  constexpr int PIECES = HPIX * 4;
-  constexpr int ITERS = (PIECES + 255) / 256;            // 6 | 9
-  __shared__ __attribute__((aligned(16))) char lds[4 * PLANE];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ox0 = blockIdx.x * 16, oy0 = blockIdx.y * TY;
   const int b = blockIdx.z / a.nslab, slab = blockIdx.z - b * a.nslab;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int q = tid & 3;                                 // this thread's 8-channel piece of every halo pixel it stages (256 % 4 == 0)
-
-  // halo pieces of this thread: input pixel index or -1 outside the image; LDS byte address or -1 behind the halo
-  int pix[ITERS], dst[ITERS];
-#pragma unroll
-  for (int it = 0; it < ITERS; ++it) {
-    const int hp = (it * 256 + tid) >> 2;
-    const int hy = hp / HW, hx = hp - hy * HW;
-    const int y = S * oy0 - 1 + hy, x = S * ox0 - 1 + hx;
-    const bool in = hp < HPIX && y >= 0 && y < a.H && x >= 0 && x < a.W;
-    pix[it] = in ? (b * a.H + y) * a.W + x : -1;
-    const int slot = hy * HW + (S == 2 ? (hx & 1) * 17 + (hx >> 1) : hx);
-    dst[it] = hp < HPIX ? q * PLANE + slot * 16 : -1;
-  }
-  uintx4_t stage[ITERS];
-  auto load_halo = [&](int c0) {
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-      stage[it] = uintx4_t{0u, 0u, 0u, 0u};
-      if (pix[it] < 0) continue;
-      if (a.in_mode == 0) {
-        if (c0 + q * 8 < a.cin) stage[it] = *reinterpret_cast<const uintx4_t*>((const half_t*)a.x + pix[it] * a.cin + c0 + q * 8);
-      } else if (q == 0) {
-        const unsigned char* p = (const unsigned char*)a.x + pix[it] * 3;
-        const half8_t v = {(half_t)(float)p[0], (half_t)(float)p[1], (half_t)(float)p[2], (half_t)0.f,
-                           (half_t)0.f,         (half_t)0.f,         (half_t)0.f,         (half_t)0.f};
-        stage[it] = __builtin_bit_cast(uintx4_t, v);
-      }
-    }
-  };
-
-  floatx4 acc[PR][NT];
-#pragma unroll
-  for (int mt = 0; mt < PR; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-
   const int kw = 9 * a.cpad;
-  const half_t* wl = a.wt + (slab * NT * 16 + fr) * kw + fq * 8;   // this lane's weight row (of the slab's fragment 0) and K piece
-  const int pix0 = fq * PLANE + (wave * PR * S * HW + fr) * 16;
-
-  constexpr bool WCHUNK = NT <= 2;
-  constexpr int WT = WCHUNK ? 9 : 2;
-  half8_t w[WT][NT];
-  auto load_w = [&](int slot, int tap, int c0) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) w[slot][nt] = *reinterpret_cast<const half8_t*>(wl + nt * 16 * kw + tap * a.cpad + c0);
-  };
-
-  load_halo(0);
-  for (int c0 = 0; c0 < a.cpad; c0 += 32) {
-    if (WCHUNK) {
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) load_w(tap, tap, c0);
-    } else {
-      load_w(0, 0, c0);
-    }
-    __syncthreads();                                    // the previous chunk's fragment reads are done
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it)
-      if (dst[it] >= 0) *reinterpret_cast<uintx4_t*>(lds + dst[it]) = stage[it];
-    __syncthreads();
-    if (c0 + 32 < a.cpad) load_halo(c0 + 32);
-
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int cur = WCHUNK ? tap : tap & 1;
-      if (!WCHUNK && tap < 8) load_w(cur ^ 1, tap + 1, c0);
-      const int ky = tap / 3, kx = tap - ky * 3;
-      const int col = S == 2 ? (kx & 1) * 17 + (kx >> 1) : kx;
-#pragma unroll
-      for (int mt = 0; mt < PR; ++mt) {
-        const half8_t px = *reinterpret_cast<const half8_t*>(lds + pix0 + ((mt * S + ky) * HW + col) * 16);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][nt], px, acc[mt][nt], 0, 0, 0);
-      }
-    }
-  }
-
-  // epilogue: lane = pixel (oy0 + PR wave + mt, ox0 + fr), channels (slab NT + nt) * 16 + fq * 4 + 0..3 (cout % 16 == 0: always whole)
-  const int x = ox0 + fr;
-  if (x >= a.Wo) return;
-#pragma unroll
-  for (int mt = 0; mt < PR; ++mt) {
-    const int y = oy0 + wave * PR + mt;
-    if (y >= a.Ho) continue;
+  conv3x3_patch<S, NT>(a, b, a.wt + slab * NT * 16 * kw, kw, a.cpad, a.cpad, a.Ho, a.Wo, [=](const floatx4& acc, int y, int x, int nt, int c4) {
     const int m = (b * a.Ho + y) * a.Wo + x;
+    const int n0 = (slab * NT + nt) * 16 + c4;
+    half4_t h;
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const int n0 = (slab * NT + nt) * 16 + fq * 4;
-      half4_t h;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float y32 = acc[mt][nt][r] * a.scale;
-        if (a.bias) y32 += a.bias[n0 + r];
-        h[r] = (half_t)(a.act ? y32 / (1.f + __expf(-y32)) : y32);
-      }
-      *reinterpret_cast<half4_t*>(a.out + m * a.cout + n0) = h;
+    for (int r = 0; r < 4; ++r) {
+      float y32 = acc[r] * a.scale;
+      if (a.bias) y32 += a.bias[n0 + r];
+      h[r] = (half_t)(a.act ? y32 / (1.f + __expf(-y32)) : y32);
     }
-  }
+    *reinterpret_cast<half4_t*>(a.out + m * a.cout + n0) = h;
+  });
 }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 template <int S>
 void launch(const HintArgs& a, int nt, dim3 grid, hipStream_t stream) {

@@ -4,27 +4,13 @@
 //                        (never materialised), optional uint8 output.  A dense block's concatenation is then a buffer layout, not a copy.
 //   af_u8_unshuffle_f16  uint8 RGB image -> fp16 NHWC in [0, 1], pixel-unshuffled by r in {1, 2, 4}, channels zero-padded to cpad.
 //
-// af_dense_conv3x3 is an implicit GEMM on v_mfma_f32_16x16x32_f16.  A workgroup of four waves owns a 16 x 16 patch of output pixels of one image
-// and all cout channels; wave w owns patch rows 4 w .. 4 w + 3.  The MFMA's A operand is the WEIGHTS (row = output channel) and its B operand the
-// PIXELS (column = the 16 pixels of one patch row), so a lane ends up with four consecutive channels of one pixel: 8-byte stores.
-// Per 32-channel chunk of the input the patch's 18 x 18 halo goes into LDS once; the nine taps read it at shifted addresses.  Halo pixels outside
-// the image are written as zeros and never read from memory, so nothing leaks from the neighbouring image of a batch.  Under `upsample` the halo is
-// filled at OUTPUT resolution from source pixel (y >> 1, x >> 1): the compute loop is the same.
-// LDS image: four planes, one per 16-byte (8-channel) piece of the chunk, each [324 halo pixels][16 bytes], plane stride 5376 bytes (a multiple of
-// the 256-byte bank row).  A B fragment is lane l -> plane l >> 4, pixel base + (l & 15): every 16-lane group of a ds_read_b128 covers sixteen
-// consecutive 16-byte slots whatever the base, which is conflict-free.  The next chunk's halo is loaded into registers ahead of the MFMAs of the
-// current one.  Weights ([npad][9 cin], at most 64 x 1728 halves, L2-resident) come straight from global memory as K-contiguous 16-byte fragments:
-// all nine taps of a chunk at once at cout <= 32, one tap ahead above that (see the main loop).
-#include "af_common.h"
+// af_dense_conv3x3 runs on the patch frame of af_conv3x3_patch.h at stride 1: a workgroup owns a 16 x 16 patch of output pixels of one image
+// and all cout channels.  This file has what is the dense kernel's own.  Its source of halo pixels is a strided NHWC buffer with bounds on the
+// OUTPUT grid: under `upsample` the halo is filled at output resolution from source pixel (y >> 1, x >> 1) and the compute loop is the same.
+// Its weights are [npad][9 cin] halves (at most 64 x 1728).  Its epilogue takes the last fragment partly filled and writes fp16 or uint8.
+#include "af_conv3x3_patch.h"
 
 namespace {
-
-constexpr int HALO = 18;
-constexpr int HALO_PIX = HALO * HALO;                  // 324
-constexpr int PLANE_BYTES = 5376;                      // 336 slots of 16 bytes: a multiple of 256
-constexpr int HALO_PIECES = HALO_PIX * 4;              // 1296 pieces of 16 bytes per chunk
-constexpr int HALO_ITERS = (HALO_PIECES + 255) / 256;  // 6
-constexpr long LIM = 1L << 31;
 
 struct DenseArgs {
   const half_t* x;
@@ -36,148 +22,72 @@ struct DenseArgs {
   int ldx, cin, ldo, cout, ldr1, ldr2;
   float alpha, beta, slope;
   int upsample, out_mode, H, W, Ho, Wo;
+
+  // the frame's Src: element offset of the piece in x
+  __device__ int locate(int b, int y, int x_, int q) const {
+    const bool in = y >= 0 && y < Ho && x_ >= 0 && x_ < Wo;
+    const int sy = upsample ? y >> 1 : y, sx = upsample ? x_ >> 1 : x_;
+    return in ? ((b * H + sy) * W + sx) * ldx + q * 8 : -1;
+  }
+  __device__ uintx4_t fetch(int h, int c0, int) const { return *reinterpret_cast<const uintx4_t*>(x + h + c0); }
 };
 
 template <int NT>
 __global__ __launch_bounds__(256) void dense_conv3x3_kernel(const DenseArgs a) {
-  __shared__ __attribute__((aligned(16))) char lds[4 * PLANE_BYTES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ox0 = blockIdx.x * 16, oy0 = blockIdx.y * 16, b = blockIdx.z;
-  const int fr = lane & 15, fq = lane >> 4;
-
-  // halo pieces of this thread: element offset into x (chunk 0) or -1 outside the image; LDS byte address
-  int src[HALO_ITERS], dst[HALO_ITERS];
-#pragma unroll
-  for (int it = 0; it < HALO_ITERS; ++it) {
-    const int idx = it * 256 + tid;
-    const int hp = idx >> 2, q = idx & 3;
-    const int hy = hp / HALO, hx = hp - hy * HALO;
-    const int y = oy0 - 1 + hy, x = ox0 - 1 + hx;
-    const bool in = idx < HALO_PIECES && y >= 0 && y < a.Ho && x >= 0 && x < a.Wo;
-    const int sy = a.upsample ? y >> 1 : y, sx = a.upsample ? x >> 1 : x;
-    src[it] = in ? ((b * a.H + sy) * a.W + sx) * a.ldx + q * 8 : -1;
-    dst[it] = idx < HALO_PIECES ? q * PLANE_BYTES + hp * 16 : -1;
-  }
-  uintx4_t stage[HALO_ITERS];
-  auto load_halo = [&](int c0) {
-#pragma unroll
-    for (int it = 0; it < HALO_ITERS; ++it) {
-      stage[it] = uintx4_t{0u, 0u, 0u, 0u};
-      if (src[it] >= 0) stage[it] = *reinterpret_cast<const uintx4_t*>(a.x + src[it] + c0);
-    }
-  };
-
-  floatx4 acc[4][NT];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-  const int kw = 9 * a.cin;
-  const half_t* wl = a.wt + fr * kw + fq * 8;           // this lane's weight row (of N tile 0) and K piece
-  const int pix0 = fq * PLANE_BYTES + (wave * 4 * HALO + fr) * 16;
-
-  // weight fragments: a whole chunk (nine taps) at once where the registers allow it (NT <= 2: 36 / 72 VGPRs), issued ahead of the halo's LDS
-  // write and its barriers so that their L2 latency is not paid tap by tap; one tap ahead otherwise.  Against one tap ahead everywhere, NT = 2 at
-  // 512 x 512: 51 -> 41 us at cin 64, 76 -> 59 us at cin 160, at 184 instead of 132 VGPRs (2 waves per SIMD instead of 3); profiles/esrgan.txt.
-  constexpr bool WCHUNK = NT <= 2;
-  constexpr int WT = WCHUNK ? 9 : 2;
-  half8_t w[WT][NT];
-  auto load_w = [&](int slot, int tap, int c0) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) w[slot][nt] = *reinterpret_cast<const half8_t*>(wl + nt * 16 * kw + tap * a.cin + c0);
-  };
-
-  load_halo(0);
-  for (int c0 = 0; c0 < a.cin; c0 += 32) {
-    if (WCHUNK) {
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) load_w(tap, tap, c0);
-    } else {
-      load_w(0, 0, c0);
-    }
-    __syncthreads();                                    // the previous chunk's fragment reads are done
-#pragma unroll
-    for (int it = 0; it < HALO_ITERS; ++it)
-      if (dst[it] >= 0) *reinterpret_cast<uintx4_t*>(lds + dst[it]) = stage[it];
-    __syncthreads();
-    if (c0 + 32 < a.cin) load_halo(c0 + 32);
-
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int cur = WCHUNK ? tap : tap & 1;
-      if (!WCHUNK && tap < 8) load_w(cur ^ 1, tap + 1, c0);
-      const int ky = tap / 3, kx = tap - ky * 3;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const half8_t px = *reinterpret_cast<const half8_t*>(lds + pix0 + ((mt + ky) * HALO + kx) * 16);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][nt], px, acc[mt][nt], 0, 0, 0);
-      }
-    }
-  }
-
-  // epilogue: lane = pixel (oy0 + 4 wave + mt, ox0 + fr), channels nt * 16 + fq * 4 + 0..3
-  const int x = ox0 + fr;
-  if (x >= a.Wo) return;
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int y = oy0 + wave * 4 + mt;
-    if (y >= a.Ho) continue;
+  const int b = blockIdx.z;
+  conv3x3_patch<1, NT>(a, b, a.wt, 9 * a.cin, a.cin, a.cin, a.Ho, a.Wo, [=](const floatx4& acc, int y, int x, int nt, int c4) {
     const int m = (b * a.Ho + y) * a.Wo + x;
+    const int n0 = nt * 16 + c4;
+    if (n0 >= a.cout) return;
+    const bool full = n0 + 4 <= a.cout;
+    const float slope = a.slope > 0.f ? a.slope : 1.f;   // no activation = slope 1: y * 1 is y, and the test stays out of the lanes' selects
+    float v[4];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const int n0 = nt * 16 + fq * 4;
-      if (n0 >= a.cout) continue;
-      const bool full = n0 + 4 <= a.cout;
-      float v[4];
+    for (int r = 0; r < 4; ++r) {
+      float y32 = acc[r];
+      if (a.bias && n0 + r < a.cout) y32 += a.bias[n0 + r];
+      v[r] = y32 >= 0.f ? y32 : slope * y32;
+    }
+    if (a.r1) {
+      const half_t* p = a.r1 + m * a.ldr1 + n0;
+      if (full) {
+        const half4_t h = *reinterpret_cast<const half4_t*>(p);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float y32 = acc[mt][nt][r];
-        if (a.bias && n0 + r < a.cout) y32 += a.bias[n0 + r];
-        v[r] = a.slope > 0.f ? (y32 >= 0.f ? y32 : a.slope * y32) : y32;
-      }
-      if (a.r1) {
-        const half_t* p = a.r1 + m * a.ldr1 + n0;
-        if (full) {
-          const half4_t h = *reinterpret_cast<const half4_t*>(p);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = a.alpha * v[r] + (float)h[r];
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (n0 + r < a.cout) v[r] = a.alpha * v[r] + (float)p[r];
-        }
-      }
-      if (a.r2) {
-        const half_t* p = a.r2 + m * a.ldr2 + n0;
-        if (full) {
-          const half4_t h = *reinterpret_cast<const half4_t*>(p);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = a.beta * v[r] + (float)h[r];
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (n0 + r < a.cout) v[r] = a.beta * v[r] + (float)p[r];
-        }
-      }
-      if (a.out_mode == 0) {
-        half_t* o = (half_t*)a.out + m * a.ldo + n0;
-        if (full) {
-          *reinterpret_cast<half4_t*>(o) = half4_t{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (n0 + r < a.cout) o[r] = (half_t)v[r];
-        }
+        for (int r = 0; r < 4; ++r) v[r] = a.alpha * v[r] + (float)h[r];
       } else {
-        unsigned char* o = (unsigned char*)a.out + m * a.cout + n0;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (n0 + r < a.cout) o[r] = (unsigned char)rintf(255.f * fminf(fmaxf(v[r], 0.f), 1.f));
+          if (n0 + r < a.cout) v[r] = a.alpha * v[r] + (float)p[r];
       }
     }
-  }
+    if (a.r2) {
+      const half_t* p = a.r2 + m * a.ldr2 + n0;
+      if (full) {
+        const half4_t h = *reinterpret_cast<const half4_t*>(p);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = a.beta * v[r] + (float)h[r];
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n0 + r < a.cout) v[r] = a.beta * v[r] + (float)p[r];
+      }
+    }
+    if (a.out_mode == 0) {
+      half_t* o = (half_t*)a.out + m * a.ldo + n0;
+      if (full) {
+        *reinterpret_cast<half4_t*>(o) = half4_t{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n0 + r < a.cout) o[r] = (half_t)v[r];
+      }
+    } else {
+      unsigned char* o = (unsigned char*)a.out + m * a.cout + n0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (n0 + r < a.cout) o[r] = (unsigned char)rintf(255.f * fminf(fmaxf(v[r], 0.f), 1.f));
+    }
+  });
 }
 
 // one lane per 8 output channels (16 bytes) of one output pixel
@@ -203,8 +113,6 @@ __global__ __launch_bounds__(256) void u8_unshuffle_f16_kernel(const unsigned ch
   }
   *reinterpret_cast<half8_t*>(out + pix * cpad + c8) = v;
 }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // A residual against out: byte ranges apart, or exactly the out elements, or other channels of the same rows (same row stride).  Anything else
 // would have one workgroup read what another writes.

@@ -110,6 +110,13 @@ def test_stride2_even_size(dev):
     check(dev, make_case(2, 20, 24, 32, 96, 2, seed=3), "2x20x24 32->96 s2")
 
 
+def test_stride2_one_fragment(dev):
+    """16 -> 16 at stride 2: the kernel instance (stride 2, one fragment per slab) that no layer of the hint encoder runs.  On the CPU:
+    max|ref| 3.4, e32 1.1e-6, in the range of the neighbouring 16-channel cases (3.9 .. 4.5, 1.7e-6)."""
+    ref = check(dev, make_case(2, 19, 21, 16, 16, 2, seed=13), "2x19x21 16->16 s2")
+    assert ref.shape == (2, 10, 11, 16)
+
+
 @pytest.mark.parametrize("H,W", [(1, 1), (1, 37)])
 @pytest.mark.parametrize("stride", [1, 2])
 def test_thin_images(dev, H, W, stride):
