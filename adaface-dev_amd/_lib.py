@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # AF_LIB: another build of the SAME sources to load instead (measurement only: tools/ab_lib.sh compares two builds of the library, e.g. one compiled
-# with -DAF_GEMM3W_DIET=0, in alternating runs on one box).  Unset in every judged run; a missing file fails as loudly as the default path.
+# with other hipcc flags or from the parent commit, in alternating runs on one box).  Unset in every judged run; a missing file fails as loudly as the default path.
 LIB_PATH = os.environ.get("AF_LIB") or os.path.join(CSRC, "libadaface_hip.so")
 
 AF_OK, AF_E_BADARG, AF_E_UNSUPPORTED, AF_E_HIP = 0, -1, -2, -3

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string>
 
 #include "../../include/adaface_hip.h"
@@ -139,6 +140,16 @@ __device__ __forceinline__ half2_t gn_half_diff(const half2_t x, const half2_t n
 // per denoise step (profiles/r03h_weight_prefetch.txt).
 constexpr int AF_WPF_MAX = 8;
 constexpr int AF_WPF_DUMP_BYTES = 256;                             // LDS the caller sets aside: 64 lanes x 4 bytes
+// The prefetch's two tunables, read once per process: AF_GEMM3_WPREFETCH = instructions per wave (default 4, 0 = off, at most AF_WPF_MAX) and
+// AF_GEMM3_WPF_COOP = the most workgroups that share one weight tile's prefetch (default 32).  A launcher passes its tiles_m and gets its (budget, coop).
+struct AfWpf {
+  int budget, coop;
+};
+inline AfWpf af_wpf_config(int tiles_m) {
+  static const int budget_env = getenv("AF_GEMM3_WPREFETCH") ? atoi(getenv("AF_GEMM3_WPREFETCH")) : 4;
+  static const int coop_env = getenv("AF_GEMM3_WPF_COOP") ? atoi(getenv("AF_GEMM3_WPF_COOP")) : 32;
+  return AfWpf{budget_env > AF_WPF_MAX ? AF_WPF_MAX : budget_env, tiles_m < coop_env ? tiles_m : coop_env};
+}
 __device__ __forceinline__ void af_prefetch_weight_tile(const half_t* wt, int kpad, int npad, int row0, int rows, int kt0, int nk, int coop, int me,
                                                         int budget, int nw, int wave, int lane, char* lds_dump) {
   const int total = rows * nk;                                   // 128-byte lines (64 halves) of these weight rows over this K range

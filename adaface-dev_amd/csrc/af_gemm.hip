@@ -577,12 +577,9 @@ int launch(const GemmDev& p0, hipStream_t stream) {
   p.tiles_n = (p.N + BN - 1) / BN;
   p.tiles_m = tiles_m;
   p.n_major = af_gemm_n_major(p.M, p.N, p.K, TAPS == 9 ? p.c1 + p.c2 : p.K);
-  {
-    static const int wpf_env = getenv("AF_GEMM3_WPREFETCH") ? atoi(getenv("AF_GEMM3_WPREFETCH")) : 4;
-    static const int coop_env = getenv("AF_GEMM3_WPF_COOP") ? atoi(getenv("AF_GEMM3_WPF_COOP")) : 32;
-    p.wpf = wpf_env > AF_WPF_MAX ? AF_WPF_MAX : wpf_env;
-    p.wpf_coop = tiles_m < coop_env ? tiles_m : coop_env;
-  }
+  const AfWpf wpf = af_wpf_config(tiles_m);
+  p.wpf = wpf.budget;
+  p.wpf_coop = wpf.coop;
   const int nk = p.kpad / BK;
   if (p.splits > nk) p.splits = nk;
   p.kt_per_split = (nk + p.splits - 1) / p.splits;

@@ -15,8 +15,6 @@
 //
 // Scope: standard epilogue (bias, per-batch row bias, SiLU / quick-GELU, residual, split-K partials); plain rows or
 // 3x3 taps with channel counts that are multiples of 32 and no upsampling.  Everything else stays on af_gemm.hip.
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "af_common.h"
@@ -47,8 +45,8 @@ struct Gemm3Dev {
   int tiles_n, tiles_m, n_major, splits, kt_per_split;
   float* ws;
   int* counters;  // in-kernel split-K reduction: one arrival counter per output tile (zero between launches); nullptr = separate reduce pass
-  int ablate;  // profiling only (AF_GEMM3_ABLATE): 1 = no DMA after the prologue, 2 = fragments read once, 4 = no barrier,
-               // 8 = no main loop, 16 = no epilogue, 32 = direct (un-staged) epilogue stores
+  int ablate;    // whole-line kernel only, A/B runs (AF_GEMM3_ABLATE, read once per process): 128 = no priority pair, 256 = no late DMA.  Kept as in
+                 // round 2: with the two as compile-time facts two 128 x 320 launches measured 1.3 - 1.8 % slower (profiles/gemm3_closed_experiments.txt)
   int stage_ok;  // output rows can be written as 16-byte chunks (N, ld_out multiples of 8, 16-byte aligned base)
   const float* ln_cs;   // LayerNorm folded into the GEMM (af_gemm_desc.ln_colsum): column sums of the packed weight, or nullptr
   float ln_eps;
@@ -118,9 +116,6 @@ __device__ __forceinline__ void glds16_sbase_masked(const half_t* sbase, unsigne
 // Every wave issues exactly 4 LDS-DMA pieces per stage in both shapes (2 A + 2 W, or 1 A + 3 W with the W pieces
 // padded from 20 to 24; padding pieces fetch the zero page), so the counted waits are the same constants.
 enum { E3_STD = 0, E3_GEGLU = 1, E3_SPLIT_T = 2 };
-#ifndef AF_GEMM3W_DIET
-#define AF_GEMM3W_DIET 1
-#endif
 
 // Epilogue shared by the ring kernel and the whole-line kernel: split-K partial tiles, or bias / row bias / activation / residual
 // (identical arithmetic to af_gemm.hip's standard epilogue), GEGLU, transposed-V split.  LDSB = bytes of LDS the main loop owned.
@@ -260,7 +255,7 @@ __device__ __forceinline__ void gemm3_epilogue(const Gemm3Dev& p, floatx4 (&acc)
   constexpr int BNO = EPI == E3_GEGLU ? BN / 2 : BN;          // output columns of the tile
   constexpr int TS = BNO + 8;                                  // staging row stride (halves): 16 bytes of padding
   constexpr bool kCanStage = (EPI == E3_STD || EPI == E3_GEGLU) && (size_t)BM * TS * 2 <= (size_t)LDSB;
-  if (kCanStage && (ROWMAP != 0 || (p.stage_ok && !(p.ablate & 32)))) {
+  if (kCanStage && (ROWMAP != 0 || p.stage_ok)) {
     __syncthreads();                                           // every wave is done reading the last ring slot
     half_t* T = reinterpret_cast<half_t*>(af_smem);
 #pragma unroll
@@ -405,7 +400,7 @@ __device__ __forceinline__ void gemm3_epilogue(const Gemm3Dev& p, floatx4 (&acc)
     const bool ok_rows = rows_side && p.split_col % 8 == 0 && p.ld_out % 8 == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;
     const bool ok_vt = vt_side && p.rows_per_batch % BM == 0 && p.ld_out2 % 8 == 0 && (reinterpret_cast<uintptr_t>(p.out2) & 15) == 0 &&
                        p.ld_out2 >= p.rows_per_batch;
-    if (kFits && (ok_rows || ok_vt) && !(p.ablate & 32)) {
+    if (kFits && (ok_rows || ok_vt)) {
       __syncthreads();                                          // every wave is done reading the last ring slot
       half_t* T = reinterpret_cast<half_t*>(af_smem);
 #pragma unroll
@@ -646,7 +641,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void af_gem
       for (int j = 0; j < APW; ++j) {
         const bool ok = (a_mask[j] >> tp) & 1u;     // tp >= 9 (K padding): no bit set
         const half_t* g = ok ? src + (size_t)(a_base[j] + dpix) * cs + coff : p.zeros;
-        if (p.ablate & 64) g = p.zeros + (((size_t)g >> 4) & 7) * 8;       // timing experiments: every DMA reads the hot 128-byte zero page
         glds16(g, As + (wave * APW + j) * 1024);
       }
     } else {
@@ -663,11 +657,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void af_gem
       }
     }
 #pragma unroll
-    for (int j = 0; j < WPW; ++j) {
-      const half_t* g = wok[j] ? wptr[j] + k0 : p.zeros;
-      if (p.ablate & 64) g = p.zeros + (((size_t)g >> 4) & 7) * 8;
-      glds16(g, Ws + (wave + NW * j) * 1024);
-    }
+    for (int j = 0; j < WPW; ++j) glds16(wok[j] ? wptr[j] + k0 : p.zeros, Ws + (wave + NW * j) * 1024);
   };
 
   floatx4 acc[TN][TM];
@@ -682,8 +672,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void af_gem
   const int nk_total = p.kpad / BK3;
   const int kt_begin = blockIdx.y * p.kt_per_split;
   const int kt_end = min(nk_total, kt_begin + p.kt_per_split);
-  int nk = kt_end - kt_begin;
-  if (p.ablate & 8) nk = 0;                       // timing experiments: launch + setup + epilogue only
+  const int nk = kt_end - kt_begin;
 
   half8_t wf[TN], xf[TM];
   // own pieces of a stage have landed when at most `younger` later stages' DMAs (DPS each, issued in order) are outstanding
@@ -728,22 +717,13 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void af_gem
       if (s < nk) issue_stage(kt_begin + s, s);
     for (int i = 0; i < nk; ++i) {
       wait_own(min(nk - 1 - i, NST - 2));
-      if (!(p.ablate & 4)) __builtin_amdgcn_s_barrier();   // every wave's pieces of stage i are in LDS; everyone is done reading slot (i-1)%NST
-      if (i + NST - 1 < nk && !(p.ablate & 1)) issue_stage(kt_begin + i + NST - 1, (i + NST - 1) % NST);
-      if (!(p.ablate & 2) || i == 0) read_frags(i % NST);
+      __builtin_amdgcn_s_barrier();                        // every wave's pieces of stage i are in LDS; everyone is done reading slot (i-1)%NST
+      if (i + NST - 1 < nk) issue_stage(kt_begin + i + NST - 1, (i + NST - 1) % NST);
+      read_frags(i % NST);
       mfma_step();
     }
   }
 
-  if (p.ablate & 16) {                            // timing experiments: no epilogue (one store keeps the accumulators alive)
-    float sacc = 0.f;
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm) sacc += acc[tn][tm][0] + acc[tn][tm][1] + acc[tn][tm][2] + acc[tn][tm][3];
-    if (sacc == 12345.678f) p.out[0] = (half_t)sacc;
-    return;
-  }
   gemm3_epilogue<EPI, NWM, NWN, TN, NST * STAGE>(p, acc, af_smem, tile_m, tile_n, wm, wn, fr, fq, tid);
 }
 
@@ -802,7 +782,10 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSLOT == 2) ? 2 
   // ---- loader state: wave w fills A pieces {w*APW + j} and W pieces {w*WPW + j}; lane = (row in piece, chunk slot)
   const int prow = lane >> 3, slot = lane & 7;
   const int Cin = p.c1 + p.c2;
-  int a_base[APW], a_lc[APW], a_par[APW];
+  int a_lc[APW];
+  // 3x3 launches only (nothing of it exists in the plain-row instantiations): the taps inside the image, the centre pixel, and for the nearest-x2
+  // gather the pixel's parity and the zero-page form of the weight pieces
+  int a_base[APW], a_par[APW];
   unsigned a_mask[APW];
   const half_t* wptr[WPW];
   bool wok[WPW];
@@ -810,8 +793,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSLOT == 2) ? 2 
   for (int j = 0; j < APW; ++j) {
     const int row = (wave * APW + j) * 8 + prow;              // row inside the tile
     a_lc[j] = slot ^ ((row >> 1) & 7);                       // logical chunk this lane fetches
-    const int m = tile_m * BM + row;
-    if (TAPS == 9) {
+    if constexpr (TAPS == 9) {
+      const int m = tile_m * BM + row;
       unsigned mk = 0;
       int base = 0;
       int par = 0;
@@ -836,18 +819,16 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSLOT == 2) ? 2 
       a_mask[j] = mk;
       a_base[j] = base;
       a_par[j] = par;
-    } else {
-      a_mask[j] = m < p.M ? 1u : 0u;
-      a_base[j] = m;
-      a_par[j] = 0;
     }
   }
+  if constexpr (TAPS == 9) {
 #pragma unroll
-  for (int j = 0; j < WPW; ++j) {
-    const int row = (wave * WPW + j) * 8 + prow;
-    const int n = tile_n * BN + row;
-    wok[j] = n < p.npad;
-    wptr[j] = p.wt + (size_t)(wok[j] ? n : 0) * p.kpad + (slot ^ ((row >> 1) & 7)) * 8;
+    for (int j = 0; j < WPW; ++j) {
+      const int row = (wave * WPW + j) * 8 + prow;
+      const int n = tile_n * BN + row;
+      wok[j] = n < p.npad;
+      wptr[j] = p.wt + (size_t)(wok[j] ? n : 0) * p.kpad + (slot ^ ((row >> 1) & 7)) * 8;
+    }
   }
   // Round 6 (vector-instruction diet, see af_conv3hd_kernel): everything per-lane about a piece's address is computed ONCE --
   //   * weight pieces and plain-row A pieces (taps 1, the K tail) use the scalar-base LDS-DMA form: a 32-bit per-lane byte offset here + a scalar
@@ -871,7 +852,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSLOT == 2) ? 2 
     const int row = (wave * APW + j) * 8 + prow;
     const int mc = min(tile_m * BM + row, p.M - 1);
     const unsigned ch = (unsigned)(a_lc[j] * 8);
-    if (TAPS == 9) {
+    if constexpr (TAPS == 9) {
       a_off1[j] = ((unsigned)mc * (unsigned)p.lda3 + ch) * 2u;
       a_off2[j] = ((unsigned)mc * (unsigned)p.lda4 + ch) * 2u;
       a_px1[j] = p.a1 + (size_t)a_base[j] * p.c1 + ch;
@@ -879,107 +860,78 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSLOT == 2) ? 2 
     } else {
       a_off1[j] = ((unsigned)mc * (unsigned)p.lda1 + ch) * 2u;
       a_off2[j] = ((unsigned)mc * (unsigned)p.lda2 + ch) * 2u;
-      a_px1[j] = a_px2[j] = nullptr;
     }
   }
-  // A/B arms: 3x3 launches keep the round-5 per-stage arithmetic behind AF_GEMM3_ABLATE bit 512 (their nearest-x2 path needs its state anyway);
-  // plain-row launches have it behind the compile-time AF_GEMM3W_DIET=0 only (a runtime switch would keep both sets of loader registers alive:
-  // the 256 x 320 GEGLU tile then spills)
-  const bool diet = TAPS == 9 ? (p.ablate & 512) == 0 : (AF_GEMM3W_DIET != 0);
 
   auto issue_stage = [&](int kt, int sl) {
     char* As = af_smem + sl * STAGE;
     char* Ws = As + BM * 128;
     const int k0 = kt * BKW;
-    if (diet && !(TAPS == 9 && p.upsample)) {
-      if (TAPS == 9 && p.c3 > 0 && k0 >= 9 * Cin) {
-        const int kt0 = k0 - 9 * Cin;                // the K tail: plain rows of a3 | a4 (64 | c3, c4: no K padding behind it)
-        const bool first = kt0 < p.c3;
-        const half_t* sb = first ? p.a3 + kt0 : p.a4 + (kt0 - p.c3);
-        // (a scalar branch, not `first ? a_off1[j] : a_off2[j]`: hipcc turns a select between two register arrays into a load from a selected
-        // ADDRESS, i.e. both arrays go to scratch)
-        if (first) {
-#pragma unroll
-          for (int j = 0; j < APW; ++j) glds16_sbase(sb, a_off1[j], As + (wave * APW + j) * 1024);
-        } else {
-#pragma unroll
-          for (int j = 0; j < APW; ++j) glds16_sbase(sb, a_off2[j], As + (wave * APW + j) * 1024);
-        }
-      } else if (TAPS == 9) {
-        const int tp = k0 / Cin;                     // workgroup-uniform (64 | c1, c2)
+    if constexpr (TAPS == 9) {
+      if (p.upsample) {
+        // nearest x2 folded into the gather (no K tail here: the host refuses c3 > 0 with upsample): per-stage arithmetic, zero page for what falls
+        // outside the image or the packed weight
+        const int tp = k0 / Cin;                    // workgroup-uniform (64 | c1, c2)
         const int c0 = k0 - tp * Cin;
         const bool first = c0 < p.c1;
+        const half_t* src = first ? p.a1 : p.a2;
         const int cs = first ? p.c1 : p.c2;
+        const int coff = first ? c0 : c0 - p.c1;
         const int ty = tp / 3, tx = tp - ty * 3;
-        const long soff = (long)((ty - 1) * p.W + (tx - 1)) * cs + (first ? c0 : c0 - p.c1);    // elements from the centre pixel's chunk: scalar
 #pragma unroll
         for (int j = 0; j < APW; ++j) {
-          const bool ok = (a_mask[j] >> tp) & 1u;
-          const half_t* px = a_px1[j];
-          if (!first) px = a_px2[j];
-          const half_t* g = ok ? px + soff : p.zeros;
+          const bool ok = (a_mask[j] >> tp) & 1u;   // tp >= 9 (K padding): no bit set
+          const int dpix = (((a_par[j] & 1) + ty - 1) >> 1) * p.W + (((a_par[j] >> 1) + tx - 1) >> 1);
+          const half_t* g = ok ? src + (size_t)(a_base[j] + dpix) * cs + coff + a_lc[j] * 8 : p.zeros;
           glds16(g, As + (wave * APW + j) * 1024);
         }
-      } else {
-        const bool first = k0 < p.c1;                // uniform: 64 | c1
-        const half_t* sb = first ? p.a1 + k0 : p.a2 + (k0 - p.c1);
-        if (first) {
 #pragma unroll
-          for (int j = 0; j < APW; ++j) glds16_sbase(sb, a_off1[j], As + (wave * APW + j) * 1024);
-        } else {
-#pragma unroll
-          for (int j = 0; j < APW; ++j) glds16_sbase(sb, a_off2[j], As + (wave * APW + j) * 1024);
-        }
+        for (int j = 0; j < WPW; ++j) glds16(wok[j] ? wptr[j] + k0 : p.zeros, Ws + (wave * WPW + j) * 1024);
+        return;
       }
-      const half_t* wb = p.wt + k0;
-#pragma unroll
-      for (int j = 0; j < WPW; ++j) glds16_sbase(wb, w_off[j], Ws + (wave * WPW + j) * 1024);
-      return;
     }
     if (TAPS == 9 && p.c3 > 0 && k0 >= 9 * Cin) {
-      // K tail: a 1x1 convolution of a second image on the output grid (stride 1: the tile row's pixel index IS its output row), c3 | c4 columns
-      const int kt0 = k0 - 9 * Cin;
-      const bool first = kt0 < p.c3;                // uniform: 64 | c3
-      const half_t* src = first ? p.a3 : p.a4;
-      const int ld = first ? p.lda3 : p.lda4;
-      const int koff = first ? kt0 : kt0 - p.c3;
-      const bool inside = kt0 < p.c3 + p.c4;        // K padding behind the tail: zeros
+      const int kt0 = k0 - 9 * Cin;                  // the K tail: plain rows of a3 | a4 (64 | c3, c4: no K padding behind it)
+      const bool first = kt0 < p.c3;
+      const half_t* sb = first ? p.a3 + kt0 : p.a4 + (kt0 - p.c3);
+      // (a scalar branch, not `first ? a_off1[j] : a_off2[j]`: hipcc turns a select between two register arrays into a load from a selected
+      // ADDRESS, i.e. both arrays go to scratch)
+      if (first) {
 #pragma unroll
-      for (int j = 0; j < APW; ++j) {
-        const bool ok = inside && ((a_mask[j] >> 4) & 1u);          // the centre tap is valid exactly for the rows m < M
-        const half_t* g = ok ? src + (size_t)a_base[j] * ld + koff + a_lc[j] * 8 : p.zeros;
-        glds16(g, As + (wave * APW + j) * 1024);
+        for (int j = 0; j < APW; ++j) glds16_sbase(sb, a_off1[j], As + (wave * APW + j) * 1024);
+      } else {
+#pragma unroll
+        for (int j = 0; j < APW; ++j) glds16_sbase(sb, a_off2[j], As + (wave * APW + j) * 1024);
       }
-    } else if (TAPS == 9) {
-      const int tp = k0 / Cin;                      // workgroup-uniform (64 | c1, c2)
+    } else if constexpr (TAPS == 9) {
+      const int tp = k0 / Cin;                       // workgroup-uniform (64 | c1, c2)
       const int c0 = k0 - tp * Cin;
       const bool first = c0 < p.c1;
-      const half_t* src = first ? p.a1 : p.a2;
       const int cs = first ? p.c1 : p.c2;
-      const int coff = first ? c0 : c0 - p.c1;
       const int ty = tp / 3, tx = tp - ty * 3;
+      const long soff = (long)((ty - 1) * p.W + (tx - 1)) * cs + (first ? c0 : c0 - p.c1);    // elements from the centre pixel's chunk: scalar
 #pragma unroll
       for (int j = 0; j < APW; ++j) {
-        const bool ok = (a_mask[j] >> tp) & 1u;     // tp >= 9 (K padding): no bit set
-        const int dpix = p.upsample ? (((a_par[j] & 1) + ty - 1) >> 1) * p.W + (((a_par[j] >> 1) + tx - 1) >> 1)
-                                    : (ty - 1) * p.W + (tx - 1);
-        const half_t* g = ok ? src + (size_t)(a_base[j] + dpix) * cs + coff + a_lc[j] * 8 : p.zeros;
+        const bool ok = (a_mask[j] >> tp) & 1u;      // tp >= 9 (K padding): no bit set
+        const half_t* px = a_px1[j];
+        if (!first) px = a_px2[j];
+        const half_t* g = ok ? px + soff : p.zeros;
         glds16(g, As + (wave * APW + j) * 1024);
       }
     } else {
-      const bool first = k0 < p.c1;                 // uniform: 64 | c1
-      const half_t* src = first ? p.a1 : p.a2;
-      const int ld = first ? p.lda1 : p.lda2;
-      const int koff = first ? k0 : k0 - p.c1;
+      const bool first = k0 < p.c1;                  // uniform: 64 | c1
+      const half_t* sb = first ? p.a1 + k0 : p.a2 + (k0 - p.c1);
+      if (first) {
 #pragma unroll
-      for (int j = 0; j < APW; ++j) {
-        const bool ok = a_mask[j] && (k0 + a_lc[j] * 8 < p.K);
-        const half_t* g = ok ? src + (size_t)a_base[j] * ld + koff + a_lc[j] * 8 : p.zeros;
-        glds16(g, As + (wave * APW + j) * 1024);
+        for (int j = 0; j < APW; ++j) glds16_sbase(sb, a_off1[j], As + (wave * APW + j) * 1024);
+      } else {
+#pragma unroll
+        for (int j = 0; j < APW; ++j) glds16_sbase(sb, a_off2[j], As + (wave * APW + j) * 1024);
       }
     }
+    const half_t* wb = p.wt + k0;
 #pragma unroll
-    for (int j = 0; j < WPW; ++j) glds16(wok[j] ? wptr[j] + k0 : p.zeros, Ws + (wave * WPW + j) * 1024);
+    for (int j = 0; j < WPW; ++j) glds16_sbase(wb, w_off[j], Ws + (wave * WPW + j) * 1024);
   };
 
   floatx4 acc[TN][TM];
@@ -1123,11 +1075,9 @@ bool launch3w(const Gemm3Dev& p0, hipStream_t stream) {
   static_assert(NSLOT == 2 || NSLOT == 4, "ring depths built: 2 and 4 (the counted waits cover at most two younger stages)");
   p.tiles_n = (p.N + BN - 1) / BN;
   p.tiles_m = (p.M + BM - 1) / BM;
-  {
-    static const int coop_env = getenv("AF_GEMM3_WPF_COOP") ? atoi(getenv("AF_GEMM3_WPF_COOP")) : 32;
-    p.wpf_coop = p.tiles_m < coop_env ? p.tiles_m : coop_env;
-    if (p.wpf > AF_WPF_MAX) p.wpf = AF_WPF_MAX;
-  }
+  const AfWpf wpf = af_wpf_config(p.tiles_m);
+  p.wpf = wpf.budget;
+  p.wpf_coop = wpf.coop;
   if (p.counters && (TN > 5 || p.splits <= 1 || p.splits > 4 || p.tiles_m * p.tiles_n > AF_SPLITK_MAX_TILES)) p.counters = nullptr;
   p.n_major = af_gemm_n_major(p.M, p.N, p.K, TAPS == 9 ? p.c1 + p.c2 : p.K);
   static bool attr_set = false;
@@ -1177,7 +1127,6 @@ constexpr int CH_BM = 256, CH_BN = 160, CH_NP_MAX = 50;          // output pixel
 constexpr int CH_ASZ = CH_NP_MAX * 1024, CH_WSZ = CH_BN * 128;   // one halo buffer, one weight stage
 constexpr int CH_LDS = 2 * CH_ASZ + 3 * CH_WSZ;                  // 163,840 B = 160 KB
 
-template <int ABL>                                                // ABL: profiling only (AF_GEMM3_ABLATE, compile-time): 1 no DMA in the loop, 2 fragments read once, 4 no barriers, 16 no MFMAs
 __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
   constexpr int NWM = 4, NWN = 2, TN = 5, TM = 4, NW = 8, BM = CH_BM, BN = CH_BN;
   constexpr int APW = (CH_NP_MAX + NW - 1) / NW;                 // 7 halo pieces per wave at most
@@ -1214,7 +1163,7 @@ __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
   const int nmain = Cin >> 6, nc1 = p.c1 >> 6;
   const int cb = blockIdx.y * p.kt_per_split;
   const int ce = min(nmain, cb + p.kt_per_split);
-  const int nst = (ABL & 8) ? 0 : (ce - cb) * 9;
+  const int nst = (ce - cb) * 9;
   struct Pos { int u, tap; };                                        // a stage = (chunk, tap)
   auto next_pos = [&](Pos q) { return q.tap < 8 ? Pos{q.u, q.tap + 1} : Pos{q.u + 1, 0}; };
   auto k0_of = [&](Pos q) { return q.tap * Cin + q.u * 64; };         // first weight column of the stage
@@ -1258,7 +1207,6 @@ __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
   };
   auto wslot = [&](int st) { return af_smem + 2 * CH_ASZ + (st % 3) * CH_WSZ; };
   auto issue_w = [&](int st, Pos q) {                                // this wave's weight pieces of stage st (at position q)
-    if constexpr ((ABL & 1) != 0) return;
     const int k0 = k0_of(q);
     char* Ws = wslot(st);
 #pragma unroll
@@ -1266,7 +1214,7 @@ __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
       if (wave + NW * j < BN / 8) glds16_nowait(wok[j] ? wptr[j] + k0 : zr, Ws + (wave + NW * j) * 1024);
   };
   auto issue_halo = [&](Pos q) {                                     // the next chunk's halo: piece j under tap j
-    if (q.u + 1 < ce && q.tap < APW && !(ABL & 1)) {
+    if (q.u + 1 < ce && q.tap < APW) {
       const half_t* src;
       int ld;
       chunk_src(q.u + 1, src, ld);
@@ -1298,7 +1246,6 @@ __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
   const int grp = wave >> 2;
   half8_t wf[TN], xf[TM], wf1[TN], xf1[TM];
   auto read_frags = [&](int st, Pos q) {
-    if ((ABL & 2) && st > 0) return;
     const char* As = af_smem + ((q.u - cb) & 1) * CH_ASZ;
     const char* Ws = wslot(st);
     const int ty = (q.tap * 11) >> 5;                                // tap / 3 for 0 .. 8 (a compare chain becomes a constant-memory table whose s_load waits on every ds_read)
@@ -1319,7 +1266,6 @@ __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
     }
   };
   auto mfmas = [&]() {
-    if constexpr ((ABL & 16) != 0) return;
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
@@ -1330,9 +1276,6 @@ __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
         acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf1[tn], xf1[tm], acc[tn][tm], 0, 0, 0);
-  };
-  auto barrier = [&]() {
-    if constexpr ((ABL & 4) == 0) __builtin_amdgcn_s_barrier();
   };
 
   __builtin_amdgcn_s_setprio(1);                                     // every wave runs at priority 1 except inside its own MFMA burst: the loaders' address
@@ -1350,69 +1293,45 @@ __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-  // ABL & 32 (timing experiments): waves 0 and 4 of workgroup 0 stamp s_memtime at the boundaries of their parts in stages 8 .. 15 into p.ws
-  // (s_memtime is a scalar memory read: only at points where no ds_read is pending, or its own lgkmcnt(0) would move them)
-  auto stamp = [&](int st, int slot_) {
-    if constexpr ((ABL & 32) != 0) {
-      if (blockIdx.x == 0 && blockIdx.y == 0 && (wave & 3) == 0 && st >= 8 && st < 16) {
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned long long t = __builtin_amdgcn_s_memtime();
-        if (lane == 0) reinterpret_cast<unsigned long long*>(p.ws)[((st - 8) * 2 + grp) * 8 + slot_] = t;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  };
   if (grp == 0) {
 #pragma nounroll
     for (int st = 0; st < nst; ++st) {
-      stamp(st, 0);
       read_frags(st, q0);
       if (st >= 1 && st + 1 < nst) issue_w(st + 1, q1);
       issue_halo(q0);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      stamp(st, 3);
       __builtin_amdgcn_sched_barrier(0);
-      barrier();                                                     // ---- end of interval 2 st
+      __builtin_amdgcn_s_barrier();                                  // ---- end of interval 2 st
       __builtin_amdgcn_sched_barrier(0);
-      stamp(st, 4);
       __builtin_amdgcn_s_setprio(0);
       mfmas();
       __builtin_amdgcn_s_setprio(1);
-      stamp(st, 5);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      stamp(st, 6);
       __builtin_amdgcn_sched_barrier(0);
-      barrier();                                                     // ---- end of interval 2 st + 1
+      __builtin_amdgcn_s_barrier();                                  // ---- end of interval 2 st + 1
       __builtin_amdgcn_sched_barrier(0);
-      stamp(st, 7);
       q0 = q1, q1 = next_pos(q1);
     }
-    barrier();                                                       // group 1's last interval
+    __builtin_amdgcn_s_barrier();                                    // group 1's last interval
   } else {
 #pragma nounroll
     for (int st = 0; st < nst; ++st) {
-      stamp(st, 0);
       if (st > 0) {                                                  // M(st - 1)
         __builtin_amdgcn_s_setprio(0);
         mfmas();
         __builtin_amdgcn_s_setprio(1);
       }
-      stamp(st, 1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      stamp(st, 2);
       __builtin_amdgcn_sched_barrier(0);
-      barrier();                                                     // ---- end of interval 2 st
+      __builtin_amdgcn_s_barrier();                                  // ---- end of interval 2 st
       __builtin_amdgcn_sched_barrier(0);
-      stamp(st, 3);
       read_frags(st, q0);
       if (st + 2 < nst) issue_w(st + 2, q2);
       issue_halo(q0);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      stamp(st, 6);
       __builtin_amdgcn_sched_barrier(0);
-      barrier();                                                     // ---- end of interval 2 st + 1
+      __builtin_amdgcn_s_barrier();                                  // ---- end of interval 2 st + 1
       __builtin_amdgcn_sched_barrier(0);
-      stamp(st, 7);
       q0 = q1, q1 = q2, q2 = next_pos(q2);
     }
     if (nst > 0) {                                                   // M(nst - 1)
@@ -1421,7 +1340,7 @@ __global__ __launch_bounds__(512) void af_conv3h_kernel(const Gemm3Dev p) {
       __builtin_amdgcn_s_setprio(1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    barrier();
+    __builtin_amdgcn_s_barrier();
   }
   __builtin_amdgcn_s_setprio(0);
   gemm3_epilogue<E3_STD, NWM, NWN, TN, CH_LDS>(p, acc, af_smem, tile_m, tile_n, wm, wn, fr, fq, tid);
@@ -1585,31 +1504,6 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
     glds16_sbase(src, (unsigned)(m0 + pc * 8 + prow) * ld2 + chunk16, af_smem + buf_off + pc * 1024);
   };
 
-#ifdef AF_CONV3H_GN_PROBE
-  // TIMING PROBE ONLY (-DAF_CONV3H_GN_PROBE, tools/probes/r06ab_gn_in_conv_probe.sh; results are NOT a convolution of the input): what the round-5 review's
-  // item 1.ii -- GroupNorm-apply + SiLU inside this kernel -- would add to the loop.  Halo piece j of chunk u, 16 bytes per lane, is read back from LDS once
-  // it has landed, turned into silu(x * g[c] * r + s) with per-channel factors from memory and written back (pad positions stay zero), one piece per
-  // stage in the L part of the stage after the one that requested it: the best schedule the loop offers.
-  const float probe_r = 1.0f + p.ln_eps, probe_s = p.ln_eps;
-  auto gn_probe_piece = [&](int j, int buf_off, int u) {
-    if (wave + NW * j < NP) {
-      char* q = af_smem + buf_off + (wave + NW * j) * 1024 + lane * 16;
-      const half8_t v = *reinterpret_cast<const half8_t*>(q);
-      const int ch = ((u * 64) & 255) + (int)(chunk16 >> 1);
-      const floatx4 g0 = *reinterpret_cast<const floatx4*>(p.bias + ch), g1 = *reinterpret_cast<const floatx4*>(p.bias + ch + 4);
-      half8_t o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float y = af_silu(fmaf((float)v[e] * (e < 4 ? g0[e] : g1[e - 4]), probe_r, probe_s));
-        o[e] = a_pix[j] >= 0 ? (half_t)y : (half_t)0.f;
-      }
-      *reinterpret_cast<half8_t*>(q) = o;
-    }
-  };
-#define CHD_GN_PROBE(TAP) if (!last && (TAP) >= 1 && (TAP) - 1 < APW) gn_probe_piece((TAP) >= 1 ? (TAP) - 1 : 0, nbuf, u + 1);
-#else
-#define CHD_GN_PROBE(TAP)
-#endif
   floatx4 acc[TN][TM];
 #pragma unroll
   for (int tn = 0; tn < TN; ++tn)
@@ -1677,12 +1571,6 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
     issue_w(cb, 1, 1);                                               // stage 1: every wave's pieces
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef AF_CONV3H_GN_PROBE
-  if (nchunks > 0) {
-#pragma unroll
-    for (int j = 0; j < APW; ++j) gn_probe_piece(j, 0, cb);
-  }
-#endif
   // the halo's out-of-image positions: zero in BOTH buffers, once (no DMA ever writes them)
 #pragma unroll
   for (int j = 0; j < APW; ++j)
@@ -1808,7 +1696,6 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
         CHD_READ_FRAGS(TAP)                                                                                                      \
         if (!(first && (TAP) == 0) && !(last && (TAP) == 8)) issue_w((TAP) < 8 ? u : u + 1, ((TAP) + 1) % 9, ((TAP) + 1) % 3);   \
         if (!last && (TAP) < APW) issue_halo_piece((TAP) < APW ? (TAP) : 0, hsrc, hld2, nbuf);                                   \
-        CHD_GN_PROBE(TAP)                                                                                                        \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                       \
         __builtin_amdgcn_sched_barrier(0);                                                                                       \
         __builtin_amdgcn_s_barrier();                                                                                            \
@@ -1852,7 +1739,6 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
         CHD_READ_FRAGS(TAP)                                                                                                      \
         if (!(last && (TAP) >= 7)) issue_w((TAP) < 7 ? u : u + 1, ((TAP) + 2) % 9, ((TAP) + 2) % 3);                             \
         if (!last && (TAP) < APW) issue_halo_piece((TAP) < APW ? (TAP) : 0, hsrc, hld2, nbuf);                                   \
-        CHD_GN_PROBE(TAP)                                                                                                        \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                       \
         __builtin_amdgcn_sched_barrier(0);                                                                                       \
         __builtin_amdgcn_s_barrier();                                                                                            \
@@ -1875,7 +1761,6 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
     __builtin_amdgcn_s_barrier();
   }
 #undef CHD_READ_FRAGS
-#undef CHD_GN_PROBE
   if (TAIL && tail_here) {
     // ---- the K tail, lock step (every wave: wait, barrier, issue the next stage, 18 fragment reads, 40 MFMAs): a tail stage moves a whole 32 KB A tile
     // + 20 KB of weights, the tap-by-tap tile's traffic, and one stage of look-ahead is all the three-slot ring and the two halo buffers allow.
@@ -1976,59 +1861,25 @@ static bool launch_conv3h(const Gemm3Dev& p0, hipStream_t stream, bool r5_loop, 
   p.tiles_m = (variant == 4 ? p.M / 4 : p.M) / CH_BM;             // (the phase form's tiles are 256 LOW-res pixels)
   p.patch_tx = p.Wo / 16;
   p.patch_tpi = p.patch_tx * (p.Ho / 16);
-  {
-    static const int coop_env = getenv("AF_GEMM3_WPF_COOP") ? atoi(getenv("AF_GEMM3_WPF_COOP")) : 32;
-    p.wpf_coop = p.tiles_m < coop_env ? p.tiles_m : coop_env;
-    if (p.wpf > AF_WPF_MAX) p.wpf = AF_WPF_MAX;
-  }
+  const AfWpf wpf = af_wpf_config(p.tiles_m);
+  p.wpf = wpf.budget;
+  p.wpf_coop = wpf.coop;
   if (p.counters && (p.splits <= 1 || p.splits > 4 || p.tiles_m * p.tiles_n > AF_SPLITK_MAX_TILES)) p.counters = nullptr;
   p.n_major = af_gemm_n_major(p.M, p.N, p.K, p.c1 + p.c2);
-  dim3 grid(p.tiles_m * p.tiles_n, p.splits), block(512);
-  if (variant == 4) {                                              // the phase form of the nearest-x2 convolution
-    static bool set_4 = false;
-    if (af_allow_dyn_lds(reinterpret_cast<const void*>(&af_conv3hd_kernel<false, 5, false, true>), CH_LDS, set_4, "af_gemm"))
-      hipLaunchKernelGGL((af_conv3hd_kernel<false, 5, false, true>), grid, block, CH_LDS, stream, p);
-    return false;
-  }
-  if (variant >= 2) {                                              // 256 x 128 tile (round 6): the diet loop only
-    static bool set_2 = false, set_3 = false;
-    if (variant == 2) {
-      if (af_allow_dyn_lds(reinterpret_cast<const void*>(&af_conv3hd_kernel<false, 4, false>), CH_LDS, set_2, "af_gemm"))
-        hipLaunchKernelGGL((af_conv3hd_kernel<false, 4, false>), grid, block, CH_LDS, stream, p);
-    } else if (af_allow_dyn_lds(reinterpret_cast<const void*>(&af_conv3hd_kernel<false, 4, true>), CH_LDS, set_3, "af_gemm")) {
-      hipLaunchKernelGGL((af_conv3hd_kernel<false, 4, true>), grid, block, CH_LDS, stream, p);
-    }
-    return p.counters != nullptr;
-  }
-#define AF_CONV3H_CASE(A)                                                                                                                     \
-  case A: {                                                                                                                                   \
-    static bool set_ = false;                                                                                                                 \
-    if (af_allow_dyn_lds(reinterpret_cast<const void*>(&af_conv3h_kernel<A>), CH_LDS, set_, "af_gemm"))                                       \
-      hipLaunchKernelGGL(af_conv3h_kernel<A>, grid, block, CH_LDS, stream, p);                                                                \
-    break;                                                                                                                                    \
-  }
-  static const bool diet_env = !(getenv("AF_CONV3H_DIET") && atoi(getenv("AF_CONV3H_DIET")) == 0);    // A/B switch: 0 = the round-5 loop
-  static const bool diet_dynamic = getenv("AF_GEMM3_ABLATE_DYNAMIC") != nullptr;
-  const bool diet = diet_dynamic ? !(getenv("AF_CONV3H_DIET") && atoi(getenv("AF_CONV3H_DIET")) == 0) : diet_env;
-  if ((diet || p.c3 > 0) && !r5_loop && (p.ablate & 63) == 0) {
-    static bool set_d = false, set_t = false;
-    if (p.c3 > 0) {
-      if (af_allow_dyn_lds(reinterpret_cast<const void*>(&af_conv3hd_kernel<true>), CH_LDS, set_t, "af_gemm"))
-        hipLaunchKernelGGL(af_conv3hd_kernel<true>, grid, block, CH_LDS, stream, p);
-    } else if (af_allow_dyn_lds(reinterpret_cast<const void*>(&af_conv3hd_kernel<false>), CH_LDS, set_d, "af_gemm")) {
-      hipLaunchKernelGGL(af_conv3hd_kernel<false>, grid, block, CH_LDS, stream, p);
-    }
-    return p.counters != nullptr;
-  }
-  switch (p.ablate & 63) {
-#ifdef AF_CONV3H_ABLATIONS                                         // timing experiments only (tools/probes/r05s_conv3hp_ablate.sh builds with this)
-    AF_CONV3H_CASE(1) AF_CONV3H_CASE(2) AF_CONV3H_CASE(3) AF_CONV3H_CASE(4) AF_CONV3H_CASE(7) AF_CONV3H_CASE(8) AF_CONV3H_CASE(16) AF_CONV3H_CASE(17) AF_CONV3H_CASE(18) AF_CONV3H_CASE(19) AF_CONV3H_CASE(32)
-#endif
-    default:
-    AF_CONV3H_CASE(0)
-  }
-#undef AF_CONV3H_CASE
-  return p.counters != nullptr;
+  // one kernel per form; all take the same argument and the same LDS.  The 256 x 160 whole-rows form (variant 1) has three: with the K tail, the
+  // round-5 loop (tile 19), and the plain round-6 loop
+  void (*kernel)(const Gemm3Dev);
+  int form;
+  if (variant == 4) form = 0, kernel = af_conv3hd_kernel<false, 5, false, true>;        // the phase form of the nearest-x2 convolution
+  else if (variant == 3) form = 1, kernel = af_conv3hd_kernel<false, 4, true>;          // 256 x 128 on patches
+  else if (variant == 2) form = 2, kernel = af_conv3hd_kernel<false, 4, false>;         // 256 x 128 on whole rows
+  else if (p.c3 > 0) form = 3, kernel = af_conv3hd_kernel<true>;
+  else if (r5_loop) form = 4, kernel = af_conv3h_kernel;
+  else form = 5, kernel = af_conv3hd_kernel<false>;
+  static bool attr_set[6] = {};
+  if (af_allow_dyn_lds(reinterpret_cast<const void*>(kernel), CH_LDS, attr_set[form], "af_gemm"))
+    hipLaunchKernelGGL(kernel, dim3(p.tiles_m * p.tiles_n, p.splits), dim3(512), CH_LDS, stream, p);
+  return p.counters != nullptr;      // (the phase form never splits: its caller passes no counters)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2430,13 +2281,10 @@ int af_gemm3_try_launch(const af_gemm_desc* d, int splits, int wide, hipStream_t
   // in-kernel split-K reduction (af_gemm_desc.splitk_fused): the last AF_SPLITK_COUNTER_BYTES of the workspace are the tile counters
   p.counters = (d->splitk_fused && d->workspace && d->workspace_bytes > AF_SPLITK_COUNTER_BYTES)
                    ? reinterpret_cast<int*>(static_cast<char*>(d->workspace) + d->workspace_bytes - AF_SPLITK_COUNTER_BYTES) : nullptr;
-  static const int wpf_env = getenv("AF_GEMM3_WPREFETCH") ? atoi(getenv("AF_GEMM3_WPREFETCH")) : 4;
-  static const bool wpf_dynamic = getenv("AF_GEMM3_ABLATE_DYNAMIC") != nullptr;
-  p.wpf = wpf_dynamic ? (getenv("AF_GEMM3_WPREFETCH") ? atoi(getenv("AF_GEMM3_WPREFETCH")) : 4) : wpf_env;
-  p.wpf_coop = 1;
+  p.wpf = 0;                                                   // the whole-line and halo launchers set the weight prefetch (af_wpf_config) once they
+  p.wpf_coop = 1;                                              // know tiles_m; the ring kernel has none
   static const int ablate = getenv("AF_GEMM3_ABLATE") ? atoi(getenv("AF_GEMM3_ABLATE")) : 0;
-  static const bool ablate_dynamic = getenv("AF_GEMM3_ABLATE_DYNAMIC") != nullptr;   // experiments: re-read per call (in-process A/B)
-  p.ablate = ablate_dynamic ? (getenv("AF_GEMM3_ABLATE") ? atoi(getenv("AF_GEMM3_ABLATE")) : 0) : ablate;
+  p.ablate = ablate & (128 | 256);                             // the whole-line kernel's two main-loop switches; nothing else reads the mask
   {
     // the whole-line kernel's loaders hold 32-bit byte offsets into the row-addressed operands (round 6): anything larger goes to the register-staged kernel
     const long ldmax = std::max(std::max((long)(d->lda1 ? d->lda1 : d->c1), (long)(d->lda2 ? d->lda2 : d->c2)), std::max((long)(d->lda3 ? d->lda3 : d->c3), (long)(d->lda4 ? d->lda4 : d->c4)));

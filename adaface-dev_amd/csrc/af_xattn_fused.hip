@@ -1252,10 +1252,8 @@ extern "C" int af_xattn_fused(const void* x, const void* wq, const void* bq, con
   static bool attr_set = false;
   if (!af_allow_dyn_lds(reinterpret_cast<const void*>(&af_xattn320_kernel), XA_LDS, attr_set, "af_xattn_fused")) return af_check_launch("af_xattn_fused");
   AfLaunchScope scope(AF_FAM_XATTN, stream);
-  // AF_XATTN_TILED (default 1): the tiled form (af_xattn320t_kernel); 0 = the wave-owns-16-tokens form.  Re-read per call under AF_GEMM3_ABLATE_DYNAMIC (A/B runs).
-  static const int tiled_env = getenv("AF_XATTN_TILED") ? atoi(getenv("AF_XATTN_TILED")) : 1;
-  static const bool dyn = getenv("AF_GEMM3_ABLATE_DYNAMIC") != nullptr;
-  const int tiled = dyn ? (getenv("AF_XATTN_TILED") ? atoi(getenv("AF_XATTN_TILED")) : 1) : tiled_env;
+  // AF_XATTN_TILED (default 1): the tiled form (af_xattn320t_kernel); 0 = the wave-owns-16-tokens form.  Read once per process.
+  static const int tiled = getenv("AF_XATTN_TILED") ? atoi(getenv("AF_XATTN_TILED")) : 1;
   if (tiled) {
     static bool attr_t = false;
     if (!af_allow_dyn_lds(reinterpret_cast<const void*>(&af_xattn320t_kernel<2>), XT_LDS, attr_t, "af_xattn_fused")) return af_check_launch("af_xattn_fused");

@@ -4,7 +4,6 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ["AF_GEMM3_ABLATE_DYNAMIC"] = "1"        # AF_GEMM3_ABLATE is re-read per launch: in-process A/B of kernel variants
 import torch
 
 from adaface_dev_amd import ops
@@ -21,9 +20,7 @@ def main():
         packs = [ops.pack_conv3x3(torch.randn(cout, cin, 3, 3) * (9 * cin) ** -0.5, torch.zeros(cout), dev) for _ in range(10)]
         flops = 2.0 * B * HW * HW * cout * 9 * cin
 
-        def graph_of(env_bits=0, **kw):
-            if env_bits:
-                os.environ["AF_GEMM3_ABLATE"] = str(env_bits)
+        def graph_of(**kw):
             for pw in packs[:2]:
                 ops.conv3x3(x, pw, **kw)
             torch.cuda.synchronize()
@@ -31,7 +28,6 @@ def main():
             with torch.cuda.graph(g):
                 for pw in packs:
                     ops.conv3x3(x, pw, **kw)
-            os.environ.pop("AF_GEMM3_ABLATE", None)
             return g
         key = f"9,{B * HW * HW},{cout},{9 * cin},0,0,1,0"
         tuned = tuple(ops.tune_table().get(key, (0, 1)))
@@ -39,7 +35,6 @@ def main():
         for sp in ({64: 1, 32: 2, 16: 4}[HW],):
             if sp <= cin // 64 and B * HW * HW // 256 * (cout // 160) * sp <= 1024:
                 variants.append((f"t14 s{sp}", graph_of(tile=14, splits=sp)))
-                variants.append((f"t14 s{sp} early-dma", graph_of(1024, tile=14, splits=sp)))
         times = {n: [] for n, _ in variants}
         for _ in range(9):                      # interleaved rounds: every variant sees the same clocks / cache state drift
             for n, g in variants:
