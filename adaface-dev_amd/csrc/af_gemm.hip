@@ -15,19 +15,12 @@
 //     conflict-free; global->register->LDS staging, double-buffered, one barrier per K step
 //     (the next tile's global loads are issued before the MFMAs of the current one);
 //   * workgroup ids are remapped so each XCD (private L2) walks a contiguous range of tiles.
-#include <stdlib.h>
-
 #include "af_common.h"
-#include <stdlib.h>
 
 // Which operand an XCD's contiguous tile range should share in its private 4 MB L2: every XCD streams the operand it does NOT
 // share in full, so share the bigger one.  Weights (N x K) beat activations (M x Cin) on the 16x16 / 8x8 levels, where the
 // default M-major mapping made all 8 XCDs fetch the whole 29.5 MB filter of a 1280 -> 1280 conv (FETCH_SIZE, profiles/r01g).
-int af_gemm_n_major(int M, int N, int K, int cin) {
-  static const int force = getenv("AF_GEMM_NMAJOR") ? atoi(getenv("AF_GEMM_NMAJOR")) : -1;
-  if (force >= 0) return force;
-  return (long)N * K > (long)M * cin ? 1 : 0;
-}
+int af_gemm_n_major(int M, int N, int K, int cin) { return (long)N * K > (long)M * cin ? 1 : 0; }
 
 namespace {
 
@@ -599,8 +592,7 @@ int launch(const GemmDev& p0, hipStream_t stream) {
 
 template <int TAPS, int EPI>
 int launch_tile(const GemmDev& p, int tile, hipStream_t stream) {
-  static const bool no_fast = getenv("AF_NO_FASTCONV") != nullptr;   // A/B switch for profiling
-  if (!no_fast && TAPS == 9 && EPI == EPI_STD && !p.upsample && p.c1 % BK == 0 && p.c2 % BK == 0) {
+  if (TAPS == 9 && EPI == EPI_STD && !p.upsample && p.c1 % BK == 0 && p.c2 % BK == 0) {
     if (tile == 1) return launch<128, 128, TAPS, EPI, true>(p, stream);
     return launch<64, 64, TAPS, EPI, true>(p, stream);
   }

@@ -11,8 +11,6 @@
 //     (<= 21 MB at batch 8) stays in the 256 MB Infinity Cache between the two passes;
 //   * the channel concat of the U-Net skip connections (openaimodel.py:918) is fused: the
 //     input is read from two sources, the output is one tensor.
-#include <stdlib.h>
-
 #include "af_common.h"
 
 namespace {
@@ -613,17 +611,15 @@ extern "C" int af_groupnorm_stats(const void* x1, const void* x2, int c1, int c2
   hipStream_t s = (hipStream_t)stream;
   AfLaunchScope scope(AF_FAM_GNORM, stream);
   // small tensors: one launch, one workgroup per (batch item, group)
-  static const bool no_small = getenv("AF_GN_NO_SMALL") != nullptr;      // A/B switch
-  if (!no_small && a.cpg % 8 == 0 && (c2 == 0 || c1 % a.cpg == 0) && (long)HW * (a.cpg / 8) <= 256L * GS_IT) {
+  if (a.cpg % 8 == 0 && (c2 == 0 || c1 % a.cpg == 0) && (long)HW * (a.cpg / 8) <= 256L * GS_IT) {
     const long nu = ((long)HW * (a.cpg / 8) + 255) / 256;     // items per thread: the instantiation with that many registers' worth of gamma / beta hoisted
     if (nu <= 2) hipLaunchKernelGGL((gn_small_kernel<2>), dim3(groups, B), dim3(256), 0, s, a);
     else if (nu <= 5) hipLaunchKernelGGL((gn_small_kernel<5>), dim3(groups, B), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((gn_small_kernel<GS_IT>), dim3(groups, B), dim3(256), 0, s, a);
     return af_check_launch("af_groupnorm(small)");
   }
-  static const bool no_pair = getenv("AF_GN_NO_PAIR") != nullptr;        // A/B switch
   // (4-byte accesses only pay while the group is small: measured 15.0 vs 19.2 us at [8, 1024, 640] but 32.8 vs 26.3 at [8, 4096, 320])
-  if (!no_small && !no_pair && a.cpg % 2 == 0 && c1 % 2 == 0 && (long)HW * (a.cpg / 2) <= 1024L * 12) {
+  if (a.cpg % 2 == 0 && c1 % 2 == 0 && (long)HW * (a.cpg / 2) <= 1024L * 12) {
     const int b8 = (B + 7) / 8 * 8;
     const long nu = ((long)HW * (a.cpg / 2) + 1023) / 1024;
     dim3 gp(b8 * groups), bp(1024);

@@ -474,10 +474,7 @@ static void launch_mix_mfma(hipStream_t s, const float* w, const half_t* x, int 
   else launch_mix_mfma_s<10, SM>(s, w, x, ldx, prob, out, ldo, alpha, B, Nq, L, heads, d);
 }
 
-static bool xattn_use_mfma(int d) {
-  static const bool off = getenv("AF_XATTN_EXPLICIT_MFMA") != nullptr && atoi(getenv("AF_XATTN_EXPLICIT_MFMA")) == 0;     // A/B switch: 0 = the wave-per-row kernels
-  return !off && d <= 160;
-}
+static bool xattn_use_mfma(int d) { return d <= 160; }      // beyond: the wave-per-row kernels
 
 bool bad_common(int B, int Nq, int L, int heads, int d) { return !(B > 0 && Nq > 0 && L > 0 && L <= 128 && heads > 0 && d > 0 && d % 8 == 0); }
 

@@ -1,6 +1,5 @@
-// af_xattn_fused.hip -- the whole cross-attention block of a C = 320 transformer layer as one launch (af_xattn_fused).
-#include <stdlib.h>
-
+// af_xattn_fused.hip -- the whole cross-attention block of a C = 320 / 640 transformer layer as one launch (af_xattn_fused), the same block behind the
+// self-attention's output projection (af_xattn_chain), and GroupNorm + proj_in at C = 320 (af_gn_proj_fused).
 #include "af_common.h"
 
 namespace {
@@ -15,27 +14,8 @@ __device__ __forceinline__ void glds16(const half_t* src, char* lds_dst) {
 //     out = x + b_o + W_o concat_h( softmax(q_h K_h^T * scale) V_h ),   q = LN(x) W_q^T          (attention.py:168-222, 242-252)
 // K / V^T come from the forward's one batched context projection (77 keys).  Unfused this is three launches per layer (to_q with the
 // LayerNorm folded in, the 77-key core, to_out with the residual: 21 + 23 + 21 us at U-Net batch 8), each too short to fill the chip.
-// A workgroup owns 128 tokens, and inside it EVERY WAVE OWNS 16 TOKENS FOR THE WHOLE BLOCK -- no data is exchanged between waves:
-//   * the wave's 16 x 320 slice of x sits in registers as the ten B-operand fragments of the q projection (its LayerNorm statistics are
-//     taken from them);
-//   * per head: Q^T [48 x 16] = W_q,h x^T (30 MFMAs; W_q,h rows in LDS, LayerNorm folded as in af_gemm_desc.ln_colsum, softmax scale folded
-//     in), S^T [80 keys x 16] = K_h Q^T, softmax over the keys of a token (the token is the lane's column: two shuffles), O^T [48 x 16] =
-//     V_h^T P^T, OUT^T [320 x 16] += W_o,h O^T (40 MFMAs, accumulated in registers over the heads) -- each product's accumulator layout
-//     (lane = token, four consecutive rows per register quad) IS the next product's B operand once the K index of that product is
-//     permuted accordingly (k slot 8 fq + j <-> row 4 fq + j of tile a for j < 4, of tile b for j >= 4), so the A operands (K_h, V_h^T,
-//     W_o,h rows in LDS) are read as two 8-byte halves per fragment and nothing goes through LDS between the four products;
-//   * LDS holds only weights / keys / values: W_q,h (30 KB), and double-buffered W_o,h (40 KB), K_h (10 KB), V_h^T (12 KB) whose next
-//     head's copies stream in under the current head; two workgroup barriers per head.
-// MEASURED (profiles/r03at_xattn_fused.txt): parity-green; 63.2 us per layer at U-Net batch 8 against 63.6 us for the three launches, -0.03 ms per
-// denoise step (three alternating runs each) -- on par alone, marginally ahead in the step (two launches fewer per layer).  First form 68 us:
-// the folded LayerNorm's column sums were loaded from global memory inside the head loop (an L2 round trip on every head's critical path) --
-// staged in LDS once: 64.0; W_o fragments requested a pair of output tiles ahead, dependent MFMAs spaced: 63.2.  What bounds it: a wave that owns
-// 16 tokens has ONE B tile, so every 1-KB weight / key / value fragment read from LDS feeds exactly one MFMA (the tiled GEMMs reuse a fragment
-// over 4 - 5 tiles): 5.8 MB of LDS reads per workgroup, and the four products of a head are a dependent chain inside the wave (Q -> S -> P -> O ->
-// OUT) that only the SIMD's second wave can overlap.  With the per-head DMA removed it still takes 59.6 us.
+// A workgroup owns 128 tokens (af_xattn320t_kernel below).
 constexpr int XA_C = 320, XA_H = 8, XA_D = 40, XA_BM = 128;
-constexpr int XA_WQ = 5 * 48 * 128, XA_WO = XA_C * 128, XA_KB = 80 * 128, XA_VB = 2 * 48 * 128;
-constexpr int XA_LDS = XA_WQ + 2 * (XA_WO + XA_KB + XA_VB) + 2 * XA_C * 4;      // 157,696 B + the folded LayerNorm's column sums and shift (2,560 B)
 
 struct XaDev {
   const half_t* x;         // [M][320] un-normalised rows
@@ -62,271 +42,21 @@ struct XaDev {
   int kpad_1;
 };
 
-__global__ __launch_bounds__(512, 1) void af_xattn320_kernel(const XaDev p) {
-  constexpr int NW = 8;
-  extern __shared__ __attribute__((aligned(16))) char af_smem[];
-  char* WQ = af_smem;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int prow = lane >> 3, slot = lane & 7;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int tile_m = blockIdx.x;
-  const int bimg = (tile_m * XA_BM) / p.N;                       // 128 | N: the tile's tokens belong to one image
-  auto WO = [&](int par) { return af_smem + XA_WQ + par * (XA_WO + XA_KB + XA_VB); };
-  auto KB_ = [&](int par) { return WO(par) + XA_WO; };
-  auto VB = [&](int par) { return WO(par) + XA_WO + XA_KB; };
-
-  // ---- loaders (1-KB LDS-DMA pieces of 8 rows x 128 B, chunk index XOR-ed with (row >> 1) & 7 on the source side)
-  auto issue_wq = [&](int h) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int pc = wave + NW * j;                              // 30 pieces: K chunk pc / 6, rows 8 (pc % 6) ..
-      if (pc < 30) {
-        const int c = pc / 6, row = (pc - c * 6) * 8 + prow;
-        const int lc = slot ^ ((row >> 1) & 7);
-        glds16(row < XA_D ? p.wq + (size_t)(h * XA_D + row) * p.kpad_q + c * 64 + lc * 8 : p.zeros, WQ + c * (48 * 128) + (pc - c * 6) * 1024);
-      }
-    }
-  };
-  auto issue_wo_k_v = [&](int h, int par) {
-    char* wo = WO(par);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {                                // 40 pieces: rows 8 pc ..
-      const int pc = wave + NW * j, row = pc * 8 + prow;
-      const int lc = slot ^ ((row >> 1) & 7);
-      glds16(lc < 5 ? p.wo + (size_t)row * p.kpad_o + h * XA_D + lc * 8 : p.zeros, wo + pc * 1024);
-    }
-    char* kb = KB_(par);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {                                // 10 pieces: keys 8 pc ..
-      const int pc = wave + NW * j;
-      if (pc < 10) {
-        const int key = pc * 8 + prow;
-        const int lc = slot ^ ((key >> 1) & 7);
-        glds16(key < p.L && lc < 5 ? p.k + ((size_t)bimg * p.L + key) * p.ldk + h * XA_D + lc * 8 : p.zeros, kb + pc * 1024);
-      }
-    }
-    char* vb = VB(par);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {                                // 12 pieces: key chunk pc / 6 (64 keys), rows 8 (pc % 6) ..
-      const int pc = wave + NW * j;
-      if (pc < 12) {
-        const int kc = pc / 6, row = (pc - kc * 6) * 8 + prow;
-        const int lc = slot ^ ((row >> 1) & 7);
-        const int key0 = kc * 64 + lc * 8;
-        glds16(row < XA_D && key0 < p.L && key0 + 8 <= p.ldv ? p.vt + (size_t)bimg * p.vbs + (size_t)(h * XA_D + row) * p.ldv + key0 : p.zeros, vb + kc * (48 * 128) + (pc - kc * 6) * 1024);
-      }
-    }
-  };
-  issue_wq(0);
-  issue_wo_k_v(0, 0);
-  // the folded LayerNorm's column sums and the projection shift of all 320 q columns: staged in LDS once (a global load per head inside the
-  // loop would put an L2 round trip on every head's critical path -- and, next to LDS-DMA loads in flight, a full vmcnt(0) drain)
-  float* csb = reinterpret_cast<float*>(af_smem + XA_WQ + 2 * (XA_WO + XA_KB + XA_VB));
-  if (tid < XA_C) {
-    csb[tid] = p.ln_on ? p.cs[tid] : 0.f;
-    csb[XA_C + tid] = p.bq ? p.bq[tid] : 0.f;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // the ds_writes above are complete before this wave reaches the loop's first barrier
-
-  // ---- this wave's 16 tokens: x^T fragments of the ten 32-wide K steps (lane = token fr, K chunk fq), LayerNorm statistics from them
-  const int m = tile_m * XA_BM + wave * 16 + fr;
-  half8_t xf[10];
-  {
-    const half_t* xr = p.x + (size_t)(m < p.M ? m : 0) * XA_C + fq * 8;
-#pragma unroll
-    for (int ks = 0; ks < 10; ++ks) xf[ks] = *reinterpret_cast<const half8_t*>(xr + ks * 32);
-  }
-  float mean = 0.f, rstd = 1.f;
-  if (p.ln_on) {
-    const half2_t one2 = {(half_t)1.0f, (half_t)1.0f};
-    float s = 0.f, q = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 10; ++ks)
-#pragma unroll
-      for (int e = 0; e < 8; e += 2) {
-        const half2_t a = {xf[ks][e], xf[ks][e + 1]};
-        s = __builtin_amdgcn_fdot2(a, one2, s, false);
-        q = __builtin_amdgcn_fdot2(a, a, q, false);
-      }
-    s += __shfl_xor(s, 16, 64);
-    q += __shfl_xor(q, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    q += __shfl_xor(q, 32, 64);
-    mean = s * (1.0f / XA_C);
-    rstd = rsqrtf(fmaxf(q * (1.0f / XA_C) - mean * mean, 0.f) + p.ln_eps);
-  }
-
-  floatx4 acc2[20];
-#pragma unroll
-  for (int nt = 0; nt < 20; ++nt) acc2[nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-  // fragment offsets inside a [rows x 128 B] region (rows are 16-aligned per tile: (row >> 1) & 7 == fr >> 1)
-  const int rd0 = fr * 128 + (((0 * 4 + fq) ^ (fr >> 1)) * 16);   // 16-byte fragments of the q projection's weights
-  const int rd1 = fr * 128 + (((1 * 4 + fq) ^ (fr >> 1)) * 16);
-  // two 8-byte halves of a permuted-K fragment: rows' elements 4 fq .. 4 fq + 3 of 16-element group g (g = 0 .. 3 -> elements 16 g ..)
-  auto off8 = [&](int g) { return fr * 128 + ((((2 * g) + (fq >> 1)) ^ (fr >> 1)) * 16) + (fq & 1) * 8; };
-  const int o8[4] = {off8(0), off8(1), off8(2), off8(3)};
-  auto frag8 = [&](const char* base, int ga, int gb) {
-    const half4_t lo = *reinterpret_cast<const half4_t*>(base + o8[ga]), hi = *reinterpret_cast<const half4_t*>(base + o8[gb]);
-    return half8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  };
-  auto pack8 = [&](const floatx4& a, const floatx4& b) {
-    return half8_t{(half_t)a[0], (half_t)a[1], (half_t)a[2], (half_t)a[3], (half_t)b[0], (half_t)b[1], (half_t)b[2], (half_t)b[3]};
-  };
-  const floatx4 zf = {0.f, 0.f, 0.f, 0.f};
-  // V^T pad: the 8-key chunk that straddles L arrives with whatever the caller's buffer holds behind key L - 1, and P = 0 does not silence an Inf / NaN
-  // there (0 x NaN = NaN in the MFMA).  Masked keys contribute NOTHING (attention.py:196-202): the halves of a V^T fragment are AND-ed with a per-lane
-  // bit mask of the live keys of its 16-key group (this lane reads keys 16 g + 4 fq + e of group g).
-  unsigned long long vmask[5];
-#pragma unroll
-  for (int g = 0; g < 5; ++g) {
-    const int live = p.L - (16 * g + 4 * fq);                    // number of live keys among this lane's four
-    vmask[g] = live >= 4 ? ~0ull : (live <= 0 ? 0ull : ((1ull << (16 * live)) - 1ull));
-  }
-  auto vfrag8 = [&](const char* base, int ga, int gb, unsigned long long ma, unsigned long long mb) {
-    unsigned long long lo = *reinterpret_cast<const unsigned long long*>(base + o8[ga]) & ma;
-    unsigned long long hi = *reinterpret_cast<const unsigned long long*>(base + o8[gb]) & mb;
-    const half4_t l4 = __builtin_bit_cast(half4_t, lo), h4 = __builtin_bit_cast(half4_t, hi);
-    return half8_t{l4[0], l4[1], l4[2], l4[3], h4[0], h4[1], h4[2], h4[3]};
-  };
-
-  for (int h = 0; h < XA_H; ++h) {
-    const int par = h & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // W_q,h and head h's W_o / K / V^T (issued a head ago) have landed
-    __builtin_amdgcn_s_barrier();                                // ... for every wave; everyone has left head h - 1
-    if (h + 1 < XA_H) issue_wo_k_v(h + 1, par ^ 1);
-    // ---- Q^T [48 x 16] = W_q,h x^T
-    floatx4 qa[3] = {zf, zf, zf};
-#pragma unroll
-    for (int c = 0; c < 5; ++c)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-          const half8_t wf = *reinterpret_cast<const half8_t*>(WQ + c * (48 * 128) + t * (16 * 128) + (kk ? rd1 : rd0));
-          qa[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, xf[2 * c + kk], qa[t], 0, 0, 0);
-        }
-    __builtin_amdgcn_s_barrier();                                // every wave is done with W_q,h
-    if (h + 1 < XA_H) issue_wq(h + 1);
-    // folded LayerNorm, projection shift, softmax scale (in log2 units); rows 40 .. 47 of the head are padding: exactly zero
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const int n = t * 16 + 4 * fq;                             // head dimension of element 0
-      floatx4 cs = zf, bq = zf;
-      if (n < XA_D) {
-        cs = *reinterpret_cast<const floatx4*>(csb + h * XA_D + n);
-        bq = *reinterpret_cast<const floatx4*>(csb + XA_C + h * XA_D + n);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) qa[t][e] = n < XA_D ? (rstd * (qa[t][e] - mean * cs[e]) + bq[e]) * p.scale_log2e : 0.f;
-    }
-    const half8_t q0 = pack8(qa[0], qa[1]), q1 = pack8(qa[2], zf);
-    // ---- S^T [80 keys x 16] = K_h Q^T (K index = head dimension, permuted as the accumulators of Q^T lie)
-    const char* kb = KB_(par);
-    floatx4 sa[5];
-    // (independent accumulators back to back: a dependent MFMA right behind its predecessor waits out the pipeline)
-#pragma unroll
-    for (int kt = 0; kt < 5; ++kt) sa[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag8(kb + kt * (16 * 128), 0, 1), q0, zf, 0, 0, 0);
-#pragma unroll
-    for (int kt = 0; kt < 5; ++kt) sa[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag8(kb + kt * (16 * 128), 2, 3), q1, sa[kt], 0, 0, 0);
-    // ---- softmax over the keys of token fr: this lane holds keys 16 kt + 4 fq + e
-    float mx = -3.0e38f;
-#pragma unroll
-    for (int kt = 0; kt < 5; ++kt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (kt * 16 + 4 * fq + e >= p.L) sa[kt][e] = -3.0e38f;
-        mx = fmaxf(mx, sa[kt][e]);
-      }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 5; ++kt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sa[kt][e] = __builtin_amdgcn_exp2f(sa[kt][e] - mx);
-        sum += sa[kt][e];
-      }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = __builtin_amdgcn_rcpf(sum);
-    // ---- O^T [48 x 16] = V_h^T P^T (K index = key, permuted as the accumulators of S^T lie: K step s = key tiles 2 s, 2 s + 1)
-    const char* vb = VB(par);
-    const half8_t p0 = pack8(sa[0], sa[1]), p1 = pack8(sa[2], sa[3]), p2 = pack8(sa[4], zf);
-    floatx4 oa[3];
-#pragma unroll
-    for (int t = 0; t < 3; ++t) oa[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vfrag8(vb + t * (16 * 128), 0, 1, vmask[0], vmask[1]), p0, zf, 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) oa[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vfrag8(vb + t * (16 * 128), 2, 3, vmask[2], vmask[3]), p1, oa[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) oa[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vfrag8(vb + 48 * 128 + t * (16 * 128), 0, 1, vmask[4], 0ull), p2, oa[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) oa[t][e] *= inv;
-    const half8_t o0 = pack8(oa[0], oa[1]), o1 = pack8(oa[2], zf);
-    // ---- OUT^T [320 x 16] += W_o,h O^T   (fragments of the next two output tiles are requested before this pair's MFMAs)
-    const char* wo = WO(par);
-    half8_t wa[2][2], wb[2][2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      wa[u][0] = frag8(wo + u * (16 * 128), 0, 1);
-      wa[u][1] = frag8(wo + u * (16 * 128), 2, 3);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 20; nt += 2) {
-      if (nt + 2 < 20) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          wb[u][0] = frag8(wo + (nt + 2 + u) * (16 * 128), 0, 1);
-          wb[u][1] = frag8(wo + (nt + 2 + u) * (16 * 128), 2, 3);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) acc2[nt + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[u][0], o0, acc2[nt + u], 0, 0, 0);
-#pragma unroll
-      for (int u = 0; u < 2; ++u) acc2[nt + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[u][1], o1, acc2[nt + u], 0, 0, 0);
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        wa[u][0] = wb[u][0];
-        wa[u][1] = wb[u][1];
-      }
-    }
-  }
-  // ---- epilogue: output bias, residual; this lane holds channels 16 nt + 4 fq + e of token fr
-  if (m < p.M) {
-#pragma unroll
-    for (int nt = 0; nt < 20; ++nt) {
-      const int c = nt * 16 + 4 * fq;
-      floatx4 v = acc2[nt];
-      if (p.bo) {
-        const floatx4 b = *reinterpret_cast<const floatx4*>(p.bo + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += b[e];
-      }
-      if (p.residual) {
-        const half4_t r = *reinterpret_cast<const half4_t*>(p.residual + (size_t)m * XA_C + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += (float)r[e];
-      }
-      const half4_t o = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-      *reinterpret_cast<half4_t*>(p.out + (size_t)m * XA_C + c) = o;
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// TILED form of the same block (round 4): the wave-owns-16-tokens kernel above reads a 1-KB fragment from LDS for every single MFMA of all four
-// products (5.8 MB per workgroup).  Here the two projections are ordinary tiled GEMMs over a token tile that stays in LDS, and the core runs
-// out of registers:
+// TILED form (round 4; what runs).  HISTORY: round 3's first form gave every wave 16 tokens for the whole block, so a wave had ONE B tile and every 1-KB
+// weight / key / value fragment read from LDS fed exactly one MFMA of the four products: 5.8 MB of LDS reads per workgroup, against 1.6 MB here
+// (profiles/r03at_xattn_fused.txt, r04g_xattn_tiled.txt).  Here the two projections are ordinary tiled GEMMs over a token tile that stays in LDS, and
+// the core runs out of registers:
 //   * R = the workgroup's 128 x 320 fp16 tile (80 KB, five 64-channel blocks of 128-byte rows, chunk index XOR (row >> 1) & 7): first x, then the
 //     attention output O in place (wave h overwrites columns 40 h .. of its own rows only after every wave has finished reading x);
 //   * phase A -- Q_h^T [48 x 128] = W_q,h x^T: WAVE h OWNS HEAD h for all 128 tokens.  W_q streams through a two-slot ring of 64-wide K stages
 //     (320 rows x 128 B = 40 KB, the whole-line GEMM's stage); a wave reads its head's 48 rows (3 A fragments) and the tile's 8 token fragments
 //     per K half: 24 MFMAs per 11 fragment reads.  LayerNorm statistics from the token fragments (folded norm2, as af_gemm_desc.ln_colsum);
 //   * phase B -- per 64-token half: S^T = K_h Q_h^T, softmax over the lane's token column, O_h^T = V_h^T P^T with the accumulators as the next
-//     product's B operand (k index permuted as in the kernel above; the 8-wide tails of d = 40 and of the 80 keys on 16x16x16 MFMAs).  K_h / V_h^T
+//     product's B operand: a 16x16 accumulator holds, per lane, the token fr and the four consecutive rows 4 fq .. 4 fq + 3, which IS a B fragment once
+//     the next product's k index is permuted to match -- k slot 8 fq + j <-> row 4 fq + j of accumulator tile a for j < 4, row 4 fq + j - 4 of tile b for
+//     j >= 4 -- so the A operands (K_h, V_h^T) are read as two 8-byte halves per fragment, 16 rows apart, and nothing goes through LDS or a shuffle
+//     between the products (the 8-wide tails of d = 40 and of the 80 keys on mfma_k16 below).  K_h / V_h^T
 //     fragments are this wave's alone: loaded ONCE from global memory into 60 registers, masked to the live keys there -- no LDS traffic at all;
 //   * phase C -- out [128 x 320] = O W_o^T + b_o + residual as a 2 x 4 wave GEMM (64 x 80 per wave) on the same ring; W_o's first two stages
 //     arrive during phase B.
@@ -336,7 +66,7 @@ constexpr int XT_STAGE = XA_C * 128;                   // 40,960: 320 weight row
 constexpr int XT_LDS = XT_R + 2 * XT_STAGE;            // 163,840
 
 // a 16-deep k tail (the 8 head dimensions 32 .. 39, the keys 64 .. 79) as a 32-deep MFMA whose upper k half is zero on both sides.
-// NOT v_mfma_f32_16x16x16_f16 (-DAF_XATTN_K16 builds it): accumulating onto the result of a 16x16x32 MFMA with the 16-deep form gave results that
+// NOT v_mfma_f32_16x16x16_f16: accumulating onto the result of a 16x16x32 MFMA with the 16-deep form gave results that
 // changed from run to run on the same inputs (hipcc 7.2, gfx950: tools/probes/r04g_xattn_debug.py localised it -- the q projection exact, single
 // (token tile, head) cells of the attention output wrong at random); with the zero-padded 32-deep form every cell is exact.
 // ROOT CAUSE (round 5, tools/probes/r05a_mfma_k16_probe.hip -> profiles/r05a_mfma_k16_probe.txt): a stand-alone chain of the two opcodes on one
@@ -344,13 +74,9 @@ constexpr int XT_LDS = XT_R + 2 * XT_STAGE;            // 163,840
 // before the 8-pass one in front of it has written it, and hipcc's gfx950 hazard recogniser inserts no wait state for that pair.  A compiler hazard
 // bug, not a race in this kernel: one opcode throughout (hardware-forwarded accumulate chain) is the fix.
 __device__ __forceinline__ floatx4 mfma_k16(const half4_t& a, const half4_t& b, const floatx4& c) {
-#ifdef AF_XATTN_K16
-  return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-#else
   const half8_t a8 = {a[0], a[1], a[2], a[3], (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
   const half8_t b8 = {b[0], b[1], b[2], b[3], (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, b8, c, 0, 0, 0);
-#endif
 }
 
 // PRE (round 6): the self-attention's to_out + residual as phase 0 in front (attention.py:242-252: x = attn1(norm1(x)) + x, then attn2 ...): the tile R first
@@ -1205,7 +931,7 @@ __global__ __launch_bounds__(512, 1) void af_gn_proj320_kernel(const GpDev p) {
 
 }  // namespace
 
-// Whole cross-attention block at C = 320 (af_xattn320_kernel above): q projection with the LayerNorm folded in (wq / bq / ln_colsum as
+// Whole cross-attention block at C = 320 (af_xattn320t_kernel<2> above; C = 640: af_xattn640t_kernel<2>): q projection with the LayerNorm folded in (wq / bq / ln_colsum as
 // ops.pack_matrix_ln packs them; ln_colsum NULL = x is used as it is), 77-key attention over this layer's slices of the batched K / V^T
 // projection, output projection, bias and residual.
 extern "C" int af_xattn_fused(const void* x, const void* wq, const void* bq, const void* ln_colsum, float ln_eps, int kpad_q, const void* k, int ldk,
@@ -1250,17 +976,9 @@ extern "C" int af_xattn_fused(const void* x, const void* wq, const void* bq, con
     return af_check_launch("af_xattn_fused(C = 640)");
   }
   static bool attr_set = false;
-  if (!af_allow_dyn_lds(reinterpret_cast<const void*>(&af_xattn320_kernel), XA_LDS, attr_set, "af_xattn_fused")) return af_check_launch("af_xattn_fused");
+  if (!af_allow_dyn_lds(reinterpret_cast<const void*>(&af_xattn320t_kernel<2>), XT_LDS, attr_set, "af_xattn_fused")) return af_check_launch("af_xattn_fused");
   AfLaunchScope scope(AF_FAM_XATTN, stream);
-  // AF_XATTN_TILED (default 1): the tiled form (af_xattn320t_kernel); 0 = the wave-owns-16-tokens form.  Read once per process.
-  static const int tiled = getenv("AF_XATTN_TILED") ? atoi(getenv("AF_XATTN_TILED")) : 1;
-  if (tiled) {
-    static bool attr_t = false;
-    if (!af_allow_dyn_lds(reinterpret_cast<const void*>(&af_xattn320t_kernel<2>), XT_LDS, attr_t, "af_xattn_fused")) return af_check_launch("af_xattn_fused");
-    hipLaunchKernelGGL(af_xattn320t_kernel<2>, dim3(p.M / XA_BM), dim3(512), XT_LDS, (hipStream_t)stream, p);
-    return af_check_launch("af_xattn_fused(tiled)");
-  }
-  hipLaunchKernelGGL(af_xattn320_kernel, dim3(p.M / XA_BM), dim3(512), XA_LDS, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(af_xattn320t_kernel<2>, dim3(p.M / XA_BM), dim3(512), XT_LDS, (hipStream_t)stream, p);
   return af_check_launch("af_xattn_fused");
 }
 

@@ -25,7 +25,7 @@ def main():
         err = float((got - ref).norm() / ref.norm())
         fl = 2.0 * B * H * N * L * d
         print(f"colmix B{B} H{H} N{N} L{L} d{d}: {ms * 1e3:.1f} us  {fl / ms / 1e9:.2f} TFLOP/s  ({w.numel() * 4 / ms / 1e6:.0f} GB/s of w)  rel-L2 vs fp64 {err:.2e}")
-        # the other explicit-attention kernels of the captured layers (round 5: MFMA forms; AF_XATTN_EXPLICIT_MFMA=0 = the wave-per-row kernels)
+        # the other explicit-attention kernels of the captured layers (round 5: MFMA forms)
         kw = dict(B=B, Nq=N, L=L, heads=H, d=d)
         q, k = x, torch.randn(B * L, H * d, device=dev).half()
         score = ops.xattn_scores(q, k, scale=d ** -0.5, **kw)

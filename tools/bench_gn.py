@@ -1,7 +1,6 @@
 """GroupNorm(+SiLU) at the denoise step's shapes (hipGraph of 20 calls each, cold-ish: a 256 MB flush between shapes is
 not done -- the producer's output normally still sits in the Infinity Cache, as here).   python tools/bench_gn.py"""
 import os
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,9 +38,4 @@ def run():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--child":
-        run()
-    else:
-        for tag, env in (("default", {}), ("no single-launch small / pair forms (AF_GN_NO_SMALL=1)", {"AF_GN_NO_SMALL": "1"})):
-            print(tag, flush=True)
-            subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=dict(os.environ, **env), check=True)
+    run()
