@@ -42,6 +42,7 @@ EXPORTS = (
     "af_dense_conv3x3", "af_u8_unshuffle_f16",
     "af_modulate_weights", "af_style_epilogue", "af_bilinear_up2", "af_face_paste_affine_u8", "af_face_align_crop_any",
     "af_hint_conv3x3",
+    "af_vit_patch_rows", "af_gelu_f16",
 )
 
 
@@ -178,6 +179,8 @@ def lib() -> C.CDLL:
     L.af_face_paste_affine_u8.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]
     L.af_face_align_crop_any.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.af_hint_conv3x3.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    L.af_vit_patch_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), i32, vp]
+    L.af_gelu_f16.argtypes = [vp, vp, i64, vp]
     L.af_prefetch.argtypes = [vp, i64, vp]
     L.af_prefetch_ex.argtypes = [vp, i64, i32, vp]
     L.af_xattn_scores.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]

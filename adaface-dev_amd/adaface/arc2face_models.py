@@ -94,20 +94,21 @@ class CLIPAttentionMKV(nn.Module):
         ps = self._qkv_params()[:3]
         return self._cache_bwd.get(ps, lambda: ops.pack_matrix(torch.cat([p.detach() for p in ps], 0).t().contiguous(), None, ps[0].device))
 
-    def hip(self, x2d, B, T, residual=None, causal=True):
-        """x2d [B*T, E] fp16 -> [B*T, E] (+ residual)."""
+    def hip(self, x2d, B, T, residual=None, causal=True, keybias=None):
+        """x2d [B*T, E] fp16 -> [B*T, E] (+ residual).  keybias: fp32 [B, >= keys] added to every score row (``ops.make_keybias``; the vision
+        towers' patch mask), None on the text path."""
         E, m = self.embed_dim, self.multiplier
         if m == 1:
             qkv = ops.gemm(x2d, self.qkv_packed())
             vt = ops.transpose_tokens(qkv[:, 2 * E:], B, T, E, 3 * E)
             o = ops.attention(qkv[:, :E], qkv[:, E:2 * E], vt, B=B, Nq=T, L=T, heads=self.num_heads, d=self.head_dim, ldq=3 * E, ldk=3 * E,
-                              scale=self.scale, causal_m=1 if causal else 0)
+                              keybias=keybias, scale=self.scale, causal_m=1 if causal else 0)
             return self.out_proj.hip(o, residual=residual)
         q = self.q_proj.hip(x2d)
         k = self.k_proj.hip(x2d).reshape(B * T * m, E)          # [B, T, m*E] rows ARE [B, T*m, E] key rows
         v = self.v_proj.hip(x2d).reshape(B * T * m, E)
         vt = ops.transpose_tokens(v, B, T * m, E, E)
-        o = ops.attention(q, k, vt, B=B, Nq=T, L=T * m, heads=self.num_heads, d=self.head_dim, ldq=E, ldk=E, scale=self.scale,
+        o = ops.attention(q, k, vt, B=B, Nq=T, L=T * m, heads=self.num_heads, d=self.head_dim, ldq=E, ldk=E, keybias=keybias, scale=self.scale,
                           causal_m=m if causal else 0)
         return self.out_proj.hip(o, residual=residual)
 
@@ -138,8 +139,13 @@ class CLIPMLP(nn.Module):
         super().__init__()
         self.fc1 = Linear(config.hidden_size, config.intermediate_size)
         self.fc2 = Linear(config.intermediate_size, config.hidden_size)
+        self.hidden_act = getattr(config, "hidden_act", "quick_gelu")
+        if self.hidden_act not in ("quick_gelu", "gelu"):
+            raise ValueError(f"CLIPMLP: hidden_act must be 'quick_gelu' or 'gelu', got {self.hidden_act!r}")
 
     def hip(self, x2d, residual=None):
+        if self.hidden_act == "gelu":                    # erf-GELU (the DINO ViT) has no af_gemm epilogue yet: one element-wise launch
+            return self.fc2.hip(ops.gelu(self.fc1.hip(x2d)), residual=residual)
         return self.fc2.hip(self.fc1.hip(x2d, act=AF_ACT_QUICKGELU), residual=residual)
 
     def hip_autograd(self, x2d, residual=None):
@@ -149,13 +155,15 @@ class CLIPMLP(nn.Module):
 class CLIPEncoderLayer(nn.Module):
     def __init__(self, config):
         super().__init__()
+        eps = getattr(config, "layer_norm_eps", 1e-5)
         self.self_attn = CLIPAttentionMKV(config, multiplier=1)
-        self.layer_norm1 = LayerNorm(config.hidden_size, eps=1e-5)
+        self.layer_norm1 = LayerNorm(config.hidden_size, eps=eps)
         self.mlp = CLIPMLP(config)
-        self.layer_norm2 = LayerNorm(config.hidden_size, eps=1e-5)
+        self.layer_norm2 = LayerNorm(config.hidden_size, eps=eps)
 
-    def hip(self, h, B, T):
-        h = self.self_attn.hip(self.layer_norm1.hip(h), B, T, residual=h)
+    def hip(self, h, B, T, causal=True, keybias=None):
+        """The text towers call this as it was (causal, no bias); the vision towers pass causal=False and their patch-mask bias."""
+        h = self.self_attn.hip(self.layer_norm1.hip(h), B, T, residual=h, causal=causal, keybias=keybias)
         return self.mlp.hip(self.layer_norm2.hip(h), residual=h)
 
     def hip_autograd(self, h, B, T):

@@ -906,6 +906,54 @@ def silu(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def gelu(x: torch.Tensor) -> torch.Tensor:
+    """erf-GELU, fp16 (af_gelu_f16): the MLP activation of DINO's ViT."""
+    _chk_f16(x, "gelu.x")
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib().af_gelu_f16(_p(x), _p(y), x.numel(), _stream()), "af_gelu_f16")
+    return y
+
+
+VIT_FILTERS = {"bilinear": 0, "bicubic": 1}
+
+
+def vit_resize_geometry(H: int, W: int, keep_aspect: bool, S: int, C: int):
+    """(Hr, Wr, top, left) of af_vit_patch_rows (the rule is in include/adaface_hip.h): torchvision's Resize(S) + CenterCrop(C), or the square
+    resize to C x C.  Python's round is half to even, as the library's."""
+    if not keep_aspect:
+        return C, C, 0, 0
+    Hr, Wr = (S, S * W // H) if H <= W else (S * H // W, S)
+    return Hr, Wr, int(round((Hr - C) / 2.0)), int(round((Wr - C) / 2.0))
+
+
+_vit_affine_cache = {}
+
+
+def _vit_affine(mean, std):
+    """The host arrays af_vit_patch_rows takes: 1 / (255 std), -mean / std (built once per normalisation)."""
+    key = (mean, std)
+    if key not in _vit_affine_cache:
+        f3 = _lib.C.c_float * 3
+        _vit_affine_cache[key] = (f3(*[1.0 / (255.0 * float(s)) for s in std]), f3(*[-float(m) / float(s) for m, s in zip(mean, std)]))
+    return _vit_affine_cache[key]
+
+
+def vit_patch_rows(images_u8: torch.Tensor, *, keep_aspect: bool, S: int, C: int, p: int, filter: str, mean, std, kpad: int = 0) -> torch.Tensor:
+    """uint8 [B, H, W, 3] device images -> fp16 [B * (C / p)^2, kpad] rows of the patch-embedding GEMM: antialiased resize, centre crop,
+    (v / 255 - mean) / std and the unfold in one launch (af_vit_patch_rows).  kpad defaults to 3 p^2 rounded up to 64."""
+    if images_u8.dtype != torch.uint8 or not images_u8.is_cuda or images_u8.dim() != 4 or images_u8.shape[3] != 3 or not images_u8.is_contiguous():
+        raise RuntimeError(f"vit_patch_rows: expected contiguous uint8 device images [B, H, W, 3], got {images_u8.dtype} {tuple(images_u8.shape)} {images_u8.device}")
+    if filter not in VIT_FILTERS:
+        raise ValueError(f"vit_patch_rows: filter must be one of {sorted(VIT_FILTERS)}, got {filter!r}")
+    B, H, W, _ = images_u8.shape
+    kpad = kpad or round_up(3 * p * p, 64)
+    rows = torch.empty((B * (C // max(p, 1)) ** 2, kpad), dtype=F16, device=images_u8.device)
+    scale, shift = _vit_affine(tuple(mean), tuple(std))
+    _lib.check(_lib.lib().af_vit_patch_rows(_p(images_u8), _p(rows), B, H, W, int(bool(keep_aspect)), int(S), int(C), int(p), VIT_FILTERS[filter],
+                                            scale, shift, kpad, _stream()), "af_vit_patch_rows")
+    return rows
+
+
 @dataclass
 class InpaintBlend:
     """The mask blend an inpaint step applies to its new latent x_new [B, 4, h, w] (INTEGRATION.md "Inpainting" rule 4):

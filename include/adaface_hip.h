@@ -671,6 +671,35 @@ int af_face_align_crop_any(const void* image_u8, const void* inv_mats, void* out
 int af_hint_conv3x3(const void* x, int in_mode, int cin, const void* wt, const void* bias, void* out, int cout, int stride, int act, int B,
                     int H, int W, void* stream);
 
+/* ---- scoring images (evaluation/vit.py, evaluation/eval_utils.py: the CLIP and DINO vision towers): the front of a ViT, one launch.
+ * img_u8 uint8 [B, H, W, 3] (RGB) -> rows fp16 [B * P][kpad], P = (C / p)^2: what torchvision's Resize / CenterCrop / Normalize (or the HF ViT
+ * feature extractor's square resize) followed by the unfold of a stride-p convolution produce, as the A operand of the patch-embedding GEMM.
+ *   Resize target (Hr, Wr): keep_aspect = 1 is Resize(S): the shorter side becomes S, the longer (S * long) / short in integer division;
+ *     keep_aspect = 0: Hr = Wr = C, S is ignored.
+ *   Resampling, separable, torch's F.interpolate(antialias=True, align_corners=False) -- the family of the rule R stated above
+ *     af_face_alpha_mask -- with a filter f of width w: filter = 0 the triangle max(0, 1 - |x|), w = 1; filter = 1 the cubic with a = -0.5,
+ *     ((a + 2) x - (a + 3)) x^2 + 1 for |x| < 1, a (((x - 5) x + 8) x - 4) for 1 <= |x| < 2, 0 beyond, w = 2.  Per axis, n_in -> n_out:
+ *     s = n_in / n_out, sc = max(s, 1), sup = w sc, c = s (i + 0.5); taps k in [max(0, int(c - sup + 0.5)), min(n_in, int(c + sup + 0.5)));
+ *     weight f((k - c + 0.5) / sc) / (its sum over the taps).  Tap ranges and the first tap's argument are formed in fp64, f and the sums
+ *     in fp32 over the values 0 .. 255 (the division by the sum of the weights last), along x, then y; no rounding and no clamp in between: cubic overshoot below 0 and above 255 is kept, as torchvision keeps it on
+ *     float tensors.  At s = 1 both filters are the identity.
+ *   Centre crop C x C of the resized image: top = rne((Hr - C) / 2), left = rne((Wr - C) / 2), half to even (torchvision's int(round(.)) is
+ *     Python's round).  Only pixels inside the crop are computed.
+ *   Value: v * scale3[c] + shift3[c], one fp32 multiply and one fp32 add, rounded to fp16 once.  scale3 / shift3: HOST arrays of three floats
+ *     (the caller passes 1 / (255 std) and -mean / std); they are read before the call returns.
+ *   Layout: row b P + py (C / p) + px; column c p^2 + dy p + dx -- the flatten order of the convolution weight [E, 3, p, p], so
+ *     weight.reshape(E, 3 p^2) is the GEMM's weight as it stands; columns 3 p^2 .. kpad - 1 are written as zeros (p = 14: 588 -> 640; a
+ *     GEMM whose K runs to kpad reads them).
+ * Any H, W >= 1, up-sizing and any ratio: the source footprint of a patch is walked in chunks, nothing is assumed to fit on chip.
+ * AF_E_BADARG before any launch (af_last_error() names the function): a NULL pointer; B, H, W, C or p below 1; C % p != 0; keep_aspect with
+ * C > S; kpad < 3 p^2 or kpad % 8 != 0; filter outside {0, 1}; B * H * W * 3 or B * P * kpad at or above 2^31; rows not 16-byte aligned.
+ * AF_E_UNSUPPORTED: p > 32.  No workspace. */
+int af_vit_patch_rows(const void* img_u8, void* rows, int B, int H, int W, int keep_aspect, int S, int C, int p, int filter,
+                      const float* scale3, const float* shift3, int kpad, void* stream);
+/* y = x * 0.5 * (1 + erf(x / sqrt(2))), fp16 in and out, fp32 inside (nn.GELU, the MLP of DINO's ViT): relative error below one fp16
+ * rounding over the whole range, the negative tail included (formed as x * erfc(-x / sqrt 2) / 2, which does not cancel) */
+int af_gelu_f16(const void* x, void* y, int64_t n, void* stream);
+
 /* ---- trainable DoRA adapters on the U-Net's up_blocks.3 convolutions (adaface/diffusers_attn_lora_capture.py:541-591; peft
  * DoraConv2dLayer.forward: y = base(x) + (s - 1) * conv(xd, W) + s * scaling * B(A(xd)), xd = dropout(x)) ---------------------
  * out = y0 + u[c] * c2 + v[c] * lb   (fp16 [rows, C]; u = s - 1, v = s * scaling, fp32 [C]) */
