@@ -1,67 +1,92 @@
-"""ctypes binding of csrc/libadaface_hip.so (C ABI declared in include/adaface_hip.h).
+"""ctypes binding of csrc/libadaface_hip.so, derived from the C ABI's own header (include/adaface_hip.h).
+
+The header is parsed once at import: every ``af_*`` prototype gives the argtypes / restype ``lib()`` sets, the body of ``af_gemm_desc``
+gives ``GemmDesc._fields_``, and every ``#define AF_*`` becomes a module attribute.  A new entry point is declared in the header and
+defined in a ``.hip`` file; nothing is added here.  The parser reads the small subset of C the header is written in and refuses anything
+else: a declaration it cannot read completely stops the import and is named in the error, it is never skipped and no type is guessed.
 
 The product path has NO fallback: if the shared library is missing or a call fails, a
 RuntimeError is raised.  ``build()`` (re)compiles the library in-tree with hipcc for gfx950.
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "adaface_hip.h")
 # AF_LIB: another build of the SAME sources to load instead (measurement only: tools/ab_lib.sh compares two builds of the library, e.g. one compiled
 # with other hipcc flags or from the parent commit, in alternating runs on one box).  Unset in every judged run; a missing file fails as loudly as the default path.
 LIB_PATH = os.environ.get("AF_LIB") or os.path.join(CSRC, "libadaface_hip.so")
 
-AF_OK, AF_E_BADARG, AF_E_UNSUPPORTED, AF_E_HIP = 0, -1, -2, -3
-AF_ACT_NONE, AF_ACT_SILU, AF_ACT_GEGLU, AF_ACT_QUICKGELU = 0, 1, 2, 3
-AF_OUT_NORMAL, AF_OUT_SPLIT_T, AF_OUT_F32 = 0, 1, 2
-AF_SPLITK_COUNTER_BYTES = 4096 * 4
-AF_FAM_GEMM, AF_FAM_ATTN, AF_FAM_GNORM, AF_FAM_LNORM, AF_FAM_ELEM, AF_FAM_XATTN = 0, 1, 2, 3, 4, 5
-
-# every symbol include/adaface_hip.h declares (tests check the .so exports exactly these)
-EXPORTS = (
-    "af_last_error", "af_version", "af_device_count", "af_prof_enable", "af_prof_reset", "af_prof_read",
-    "af_gemm", "af_groupnorm_ws_floats", "af_groupnorm", "af_layernorm", "af_attention", "af_attention_scores",
-    "af_timestep_embedding", "af_nchw_f32_to_nhwc_f16", "af_nhwc_f16_to_nchw_f32", "af_cfg_ddim_step", "af_q_sample",
-    "af_silu_f16", "af_attention_lse", "af_groupnorm_stats", "af_attention_bwd_scratch_bytes", "af_attention_bwd",
-    "af_groupnorm_bwd", "af_layernorm_bwd", "af_geglu_fwd", "af_geglu_bwd", "af_sumpool2x2", "af_add_f16",
-    "af_transpose_tokens", "af_cadamw_step", "af_attention_ex", "af_colsum", "af_quickgelu_fwd", "af_quickgelu_bwd",
-    "af_scale_f32", "af_affine_prelu", "af_maxpool2x2", "af_global_avgpool", "af_se_residual_prelu", "af_axpy_f16", "af_dora_combine", "af_mul_f16", "af_im2col3x3", "af_colsum_tall", "af_softmax_rows", "af_attention_strided", "af_clamp_f32", "af_mask_pairs", "af_prefetch", "af_prefetch_ex",
-    "af_xattn_scores", "af_xattn_softmax_pv", "af_xattn_softmax_pv_bwd", "af_xattn_rowmix", "af_xattn_colmix_ws_bytes", "af_xattn_colmix",
-    "af_layernorm_param_grads", "af_transpose_tokens_pair", "af_ff_fused", "af_ff_chain", "af_xattn_fused",
-    "af_softmax_rows_bwd", "af_affine_prelu_bwd", "af_maxpool2x2_bwd", "af_se_gate_grad", "af_se_residual_prelu_bwd",
-    "af_groupnorm_apply", "af_gemm_gn_stats_ok", "af_gemm_halo_variant", "af_gn_proj_fused",
-    "af_xattn_chain",
-    "af_image_u8_to_nhwc_f16", "af_vae_latents_q_sample", "af_cfg_dpmpp_step", "af_cfg_lcm_step",
-    "af_cfg_ddim_inpaint_step", "af_cfg_dpmpp_inpaint_step", "af_cfg_lcm_inpaint_step", "af_vae_latents_z_q_sample",
-    "af_vae_attention", "af_latent_resize_q_sample", "af_affine_prelu_ch", "af_face_align_crop",
-    "af_stem_im2col7x7", "af_relu_maxpool3x3s2", "af_subsample2x", "af_upsample2x_add", "af_retina_decode", "af_retina_nms",
-    "af_face_alpha_mask", "af_crop_resize_u8", "af_paste_back_u8",
-    "af_temporal_attention",
-    "af_dense_conv3x3", "af_u8_unshuffle_f16",
-    "af_modulate_weights", "af_style_epilogue", "af_bilinear_up2", "af_face_paste_affine_u8", "af_face_align_crop_any",
-    "af_hint_conv3x3",
-    "af_vit_patch_rows", "af_gelu_f16",
-)
-
 
 class GemmDesc(C.Structure):
-    _fields_ = [
-        ("a1", C.c_void_p), ("a2", C.c_void_p), ("wt", C.c_void_p), ("bias", C.c_void_p),
-        ("rowbias", C.c_void_p), ("residual", C.c_void_p), ("out", C.c_void_p), ("out2", C.c_void_p),
-        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("kpad", C.c_int32), ("taps", C.c_int32),
-        ("c1", C.c_int32), ("c2", C.c_int32), ("lda1", C.c_int32), ("lda2", C.c_int32),
-        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32),
-        ("stride", C.c_int32), ("upsample", C.c_int32), ("rows_per_batch", C.c_int32), ("ld_rowbias", C.c_int32),
-        ("act", C.c_int32), ("out_mode", C.c_int32), ("ld_out", C.c_int32), ("split_col", C.c_int32),
-        ("ld_out2", C.c_int32), ("tile", C.c_int32), ("splits", C.c_int32),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("zeros", C.c_void_p),
-        ("tap_shift", C.c_int32), ("splitk_fused", C.c_int32),
-        ("ln_colsum", C.c_void_p), ("ln_eps", C.c_float),
-        ("a3", C.c_void_p), ("a4", C.c_void_p), ("c3", C.c_int32), ("c4", C.c_int32), ("lda3", C.c_int32), ("lda4", C.c_int32),
-        ("gn_partials", C.c_void_p), ("gn_cpg", C.c_int32),
-    ]
+    """af_gemm_desc.  Its _fields_ are the header's struct members, set below."""
+
+
+# Every type spelling the header may use (one space between words, none before '*') and its ctypes type.
+CTYPES = {
+    "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float,
+    "void*": C.c_void_p, "const void*": C.c_void_p, "const char*": C.c_char_p,
+    "const float*": C.POINTER(C.c_float), "const int*": C.POINTER(C.c_int), "int*": C.POINTER(C.c_int), "double*": C.POINTER(C.c_double),
+    "const af_gemm_desc*": C.POINTER(GemmDesc),
+}
+
+
+_DECLARATOR = re.compile(r"(.+?)\b(\w+(?:\s*,\s*\w+)*)")
+
+
+def _declarator(decl: str, where: str):
+    """'const void* a1' -> ('const void*', ['a1']); 'int32_t M, N, K' -> ('int32_t', ['M', 'N', 'K'])."""
+    m = _DECLARATOR.fullmatch(decl.strip())
+    spelling = " ".join(m.group(1).replace("*", " * ").split()).replace(" *", "*") if m else None
+    if spelling not in CTYPES:
+        raise RuntimeError(f"adaface_hip.h: cannot read {' '.join(decl.split())!r} in {where!r}: expected '<type> <name>' with a type out of {sorted(CTYPES)}")
+    return spelling, [n.strip() for n in m.group(2).split(",")]
+
+
+def parse_header(text: str):
+    """The ABI a header text declares, as spellings: (functions {name: (return type, [parameter types])} in declaration order,
+    fields [(member of af_gemm_desc, type)], constants {AF_*: int}).  RuntimeError for anything that is not read completely."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(AF_\w+)(.*)$", text, flags=re.M):
+        try:                                                    # an integer, or arithmetic over the constants above it
+            if not re.fullmatch(r"[\w\s()*+-]+", value):
+                raise ValueError("not integer arithmetic")
+            constants[name] = int(eval(value, {"__builtins__": {}}, constants))
+        except Exception as e:
+            raise RuntimeError(f"adaface_hip.h: cannot read '#define {name}{value}': {e}") from e
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    fields = []
+    m = re.search(r"typedef\s+struct\s+af_gemm_desc\s*\{(.*?)\}\s*af_gemm_desc\s*;", text, flags=re.S)
+    if m:
+        for decl in filter(str.strip, m.group(1).split(";")):
+            spelling, names = _declarator(decl, "af_gemm_desc")
+            fields += [(n, spelling) for n in names]
+        text = text[:m.start()] + text[m.end():]
+    functions = {}
+    for decl in filter(str.strip, text.split(";")):
+        proto = " ".join(decl.split())
+        m = re.fullmatch(r"([^()]+)\(([^()]*)\)", proto)
+        if not m:
+            raise RuntimeError(f"adaface_hip.h: cannot read the declaration {proto!r}")
+        ret, names = _declarator(m.group(1), proto)
+        if len(names) != 1 or not names[0].startswith("af_") or names[0] in functions:
+            raise RuntimeError(f"adaface_hip.h: cannot read the declaration {proto!r}: expected one new af_* function")
+        functions[names[0]] = (ret, [] if m.group(2).strip() == "void" else [_declarator(p, proto)[0] for p in m.group(2).split(",")])
+    return functions, fields, constants
+
+
+with open(HEADER) as _f:
+    FUNCTIONS, _fields, _constants = parse_header(_f.read())
+if not _fields:
+    raise RuntimeError("adaface_hip.h: no af_gemm_desc")
+GemmDesc._fields_ = [(n, CTYPES[t]) for n, t in _fields]
+globals().update(_constants)                                    # AF_OK, AF_E_*, AF_ACT_*, AF_OUT_*, AF_FAM_*, AF_SPLITK_*, ...
+EXPORTS = tuple(FUNCTIONS)                                      # every symbol the header declares (tests check the .so exports exactly these)
 
 
 def _csrc_sha() -> str:
@@ -69,7 +94,7 @@ def _csrc_sha() -> str:
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")))
-    files += [os.path.join(CSRC, "Makefile"), os.path.join(os.path.dirname(_HERE), "include", "adaface_hip.h")]
+    files += [os.path.join(CSRC, "Makefile"), HEADER]
     for f in files:
         h.update(os.path.basename(f).encode())
         with open(f, "rb") as fh:
@@ -123,117 +148,9 @@ def lib() -> C.CDLL:
             "Run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C adaface-dev_amd/csrc`."
         )
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
-    L.af_last_error.restype = C.c_char_p
-    L.af_last_error.argtypes = []
-    L.af_version.argtypes = []
-    L.af_device_count.argtypes = []
-    L.af_prof_enable.argtypes = [i32]
-    L.af_prof_reset.argtypes = []
-    L.af_prof_read.argtypes = [i32, C.POINTER(C.c_int), C.POINTER(C.c_double)]
-    L.af_gemm.argtypes = [C.POINTER(GemmDesc), vp]
-    L.af_groupnorm_ws_floats.argtypes = [i32]
-    L.af_groupnorm.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]
-    L.af_groupnorm_apply.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, i32, vp]
-    L.af_gemm_gn_stats_ok.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32]
-    L.af_gemm_halo_variant.argtypes = [C.POINTER(GemmDesc)]
-    L.af_gn_proj_fused.argtypes = [vp, vp, i32, vp, vp, f32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp]
-    L.af_layernorm.argtypes = [vp, vp, vp, vp, i32, i32, f32, vp]
-    L.af_attention.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]
-    L.af_attention_scores.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
-    L.af_timestep_embedding.argtypes = [vp, vp, i32, i32, f32, vp]
-    L.af_nchw_f32_to_nhwc_f16.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    L.af_nhwc_f16_to_nchw_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    L.af_cfg_ddim_step.argtypes = [vp, vp, vp, vp, i64, i32, f32, f32, f32, vp]
-    L.af_cfg_dpmpp_step.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, f32, vp]
-    L.af_cfg_lcm_step.argtypes = [vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, f32, f32, vp]
-    L.af_q_sample.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp]
-    L.af_image_u8_to_nhwc_f16.argtypes = [vp, vp, i32, i32, i32, vp]
-    L.af_vae_latents_q_sample.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, vp, i32, i32, i32, i32, vp]
-    L.af_vae_latents_z_q_sample.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, i32, i32, i32, i32, vp]
-    L.af_latent_resize_q_sample.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, vp]
-    blend = [vp, vp, vp, i32, i32, i64, f32, f32]
-    L.af_cfg_ddim_inpaint_step.argtypes = L.af_cfg_ddim_step.argtypes[:-1] + blend + [vp]
-    L.af_cfg_dpmpp_inpaint_step.argtypes = L.af_cfg_dpmpp_step.argtypes[:-1] + blend + [vp]
-    L.af_cfg_lcm_inpaint_step.argtypes = L.af_cfg_lcm_step.argtypes[:-1] + blend + [vp]
-    L.af_silu_f16.argtypes = [vp, vp, i64, vp]
-    L.af_attention_lse.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]
-    L.af_attention_ex.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]
-    L.af_attention_strided.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, f32, vp]
-    L.af_groupnorm_stats.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]
-    L.af_attention_bwd_scratch_bytes.argtypes = [i32, i32, i32, i32, i32]
-    L.af_attention_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i64] + [i32] * 14 + [f32, vp]
-    L.af_axpy_f16.argtypes = [vp, vp, f32, vp, i64, vp]
-    L.af_dora_combine.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, vp]
-    L.af_mul_f16.argtypes = [vp, vp, vp, i64, vp]
-    L.af_im2col3x3.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-    L.af_softmax_rows.argtypes = [vp, vp, i64, i32, vp]
-    L.af_mask_pairs.argtypes = [vp, vp, i32, vp]
-    L.af_vae_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    L.af_temporal_attention.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
-    L.af_dense_conv3x3.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, f32, vp, i32, f32, f32, i32, i32, i32, i32, i32, vp]
-    L.af_u8_unshuffle_f16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-    L.af_modulate_weights.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
-    L.af_style_epilogue.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]
-    L.af_bilinear_up2.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.af_face_paste_affine_u8.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]
-    L.af_face_align_crop_any.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.af_hint_conv3x3.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    L.af_vit_patch_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), i32, vp]
-    L.af_gelu_f16.argtypes = [vp, vp, i64, vp]
-    L.af_prefetch.argtypes = [vp, i64, vp]
-    L.af_prefetch_ex.argtypes = [vp, i64, i32, vp]
-    L.af_xattn_scores.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp]
-    L.af_xattn_softmax_pv.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    L.af_xattn_softmax_pv_bwd.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]
-    L.af_xattn_rowmix.argtypes = [vp, vp, i32, vp, i32, f32, i32, i32, i32, i32, i32, vp]
-    L.af_xattn_colmix_ws_bytes.argtypes = [i32, i32, i32, i32]
-    L.af_xattn_colmix.argtypes = [vp, vp, i32, vp, i32, f32, vp, i64, i32, i32, i32, i32, i32, vp]
-    L.af_colsum.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    L.af_colsum_tall.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.af_quickgelu_fwd.argtypes = [vp, vp, i64, vp]
-    L.af_quickgelu_bwd.argtypes = [vp, vp, vp, i64, vp]
-    L.af_scale_f32.argtypes = [vp, f32, i64, vp]
-    L.af_clamp_f32.argtypes = [vp, f32, f32, i64, vp]
-    L.af_affine_prelu.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp]
-    L.af_affine_prelu_ch.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp]
-    L.af_face_align_crop.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.af_stem_im2col7x7.argtypes = [vp, C.POINTER(f32), C.POINTER(f32), vp, i32, i32, i32, i32, vp]
-    L.af_relu_maxpool3x3s2.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    L.af_subsample2x.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    L.af_upsample2x_add.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.af_retina_decode.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, f32, vp, vp, i32, vp]
-    L.af_retina_nms.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, vp]
-    L.af_face_alpha_mask.argtypes = [vp, vp, i32, i32, i32, f32, vp]
-    L.af_crop_resize_u8.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]
-    L.af_paste_back_u8.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-    L.af_maxpool2x2.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    L.af_global_avgpool.argtypes = [vp, vp, i32, i32, i32, vp]
-    L.af_se_residual_prelu.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    L.af_softmax_rows_bwd.argtypes = [vp, vp, vp, i64, i32, vp]
-    L.af_affine_prelu_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, vp]
-    L.af_maxpool2x2_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.af_se_gate_grad.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    L.af_se_residual_prelu_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    L.af_groupnorm_bwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    L.af_layernorm_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, vp]
-    L.af_layernorm_param_grads.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, vp]
-    L.af_geglu_fwd.argtypes = [vp, vp, i64, i32, vp]
-    L.af_geglu_bwd.argtypes = [vp, vp, vp, i64, i32, vp]
-    L.af_sumpool2x2.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    L.af_add_f16.argtypes = [vp, vp, vp, i64, vp]
-    L.af_transpose_tokens.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-    L.af_transpose_tokens_pair.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
-    L.af_cadamw_step.argtypes = [vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, f32, i32, i32, vp]
-    L.af_ff_fused.argtypes = [vp, vp, vp, vp, f32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp]
-    L.af_ff_chain.argtypes = [vp, vp, vp, vp, f32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
-    L.af_xattn_fused.argtypes = [vp, vp, vp, vp, f32, i32, vp, i32, vp, i64, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp]
-    L.af_xattn_chain.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, i32, vp, i32, vp, i64, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp, vp]
-    for name in EXPORTS:
-        if name != "af_last_error":
-            getattr(L, name).restype = C.c_int
-    L.af_attention_bwd_scratch_bytes.restype = C.c_int64
-    L.af_xattn_colmix_ws_bytes.restype = C.c_int64
+    for name, (ret, params) in FUNCTIONS.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = CTYPES[ret], [CTYPES[p] for p in params]
     _lib = L
     return L
 

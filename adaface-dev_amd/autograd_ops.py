@@ -15,7 +15,7 @@ fp16 AMP does in the reference (`precision: 16` Lightning runs); parameter gradi
 dtype (fp32 master weights) still multiplied by that scale and are unscaled in the flat gradient arena."""
 import torch
 
-from . import _lib, ops
+from . import ops
 from .ops import F16, round_up
 
 
@@ -34,9 +34,7 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     xt = torch.empty((k128, m64), dtype=F16, device=dev)
     if k128 != K:
         xt[K:].zero_()                                                         # only the pad rows (the packed-weight layout wants 128-row multiples)
-    L = _lib.lib()
-    _lib.check(L.af_transpose_tokens_pair(ops._p(dy), ops._p(dyt), N, N, ops._p(x), ops._p(xt), K, K, 1, M, m64, ops._stream()),
-               "af_transpose_tokens_pair")                                     # both operands in one launch
+    ops._launch("af_transpose_tokens_pair", ops._p(dy), ops._p(dyt), N, N, ops._p(x), ops._p(xt), K, K, 1, M, m64)     # both operands in one launch
     pw = ops.PackedWeight(xt, None, K, m64, m64, 1, m64)
     return ops.gemm(dyt, pw, out_f32=True)
 

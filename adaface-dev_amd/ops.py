@@ -43,6 +43,20 @@ def _stream() -> int:
     return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
 
 
+def _checked(name: str, *args) -> int:
+    """Call the library's entry point ``name`` with ``args`` as they stand; RuntimeError (naming it) if it fails."""
+    rc = getattr(_lib.lib(), name)(*args)
+    _lib.check(rc, name)
+    return rc
+
+
+def _launch(name: str, *args, what: Optional[str] = None) -> int:
+    """The same for a launch: ``args`` are the entry point's arguments up to its last one, the stream, which is the current one."""
+    rc = getattr(_lib.lib(), name)(*args, _stream())
+    _lib.check(rc, what or name)
+    return rc
+
+
 def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
@@ -339,7 +353,7 @@ class WeightPrefetcher:
                 ev = torch.cuda.Event()
                 ev.record()                                  # the main stream's position: everything before launch i
                 self.side.wait_event(ev)
-                _lib.check(_lib.lib().af_prefetch_ex(self.plan[j][0], self.plan[j][1], self.max_wg, self.side.cuda_stream), "af_prefetch_ex")
+                _checked("af_prefetch_ex", self.plan[j][0], self.plan[j][1], self.max_wg, self.side.cuda_stream)
                 self.issued += 1
 
     def join(self):
@@ -415,7 +429,7 @@ def _launch_gemm(d: "GemmDesc", device, what: str, tile: int = 0, splits: int = 
             d.gn_partials, d.gn_cpg = gn.ws.data_ptr(), gn_cpg
     if _weight_prefetcher is not None and _weight_prefetcher.mode is not None:
         _weight_prefetcher.note(int(d.wt), int(d.kpad) * round_up(int(d.N) * (4 if d.upsample == 3 else 1), 128) * 2)
-    _lib.check(_lib.lib().af_gemm(C.byref(d), _stream()), what)
+    _launch("af_gemm", C.byref(d), what=what)
     return gn
 
 
@@ -596,9 +610,8 @@ def ff_fused(x2d: torch.Tensor, pw1: PackedWeight, pw2: PackedWeight, residual: 
         _chk_f16(residual, "ff_fused.residual")
         assert residual.shape == out.shape
     _pf_note(pw1.wt, pw2.wt)
-    rc = _lib.lib().af_ff_fused(_p(x2d), _p(pw1.wt), _p(pw1.bias), _p(pw1.ln_cs), float(pw1.ln_eps), pw1.kpad, _p(pw2.wt), _p(pw2.bias), pw2.kpad,
-                                _p(residual), _p(out), M, Cn, pw2.K, _p(_zero_page(x2d.device)), _stream())
-    _lib.check(rc, "af_ff_fused")
+    _launch("af_ff_fused", _p(x2d), _p(pw1.wt), _p(pw1.bias), _p(pw1.ln_cs), float(pw1.ln_eps), pw1.kpad, _p(pw2.wt), _p(pw2.bias), pw2.kpad,
+            _p(residual), _p(out), M, Cn, pw2.K, _p(_zero_page(x2d.device)))
     return out
 
 
@@ -618,10 +631,9 @@ def ff_chain(x2d: torch.Tensor, pw1: PackedWeight, pw2: PackedWeight, residual: 
         gn = GnPartials.alloc(x2d.device, M // rows_per_batch, rows_per_batch, Cn, gn_cpg)
         gnp = gn.ws.data_ptr()
     _pf_note(pw1.wt, pw2.wt, pw_p.wt)
-    rc = _lib.lib().af_ff_chain(_p(x2d), _p(pw1.wt), _p(pw1.bias), _p(pw1.ln_cs), float(pw1.ln_eps), pw1.kpad, _p(pw2.wt), _p(pw2.bias), pw2.kpad, _p(residual),
-                                _p(pw_p.wt), _p(pw_p.bias), pw_p.kpad, _p(x_in), _p(out), gnp, int(gn_cpg if gn is not None else 0), int(rows_per_batch), M, Cn, pw2.K,
-                                _p(_zero_page(x2d.device)), _stream())
-    _lib.check(rc, "af_ff_chain")
+    _launch("af_ff_chain", _p(x2d), _p(pw1.wt), _p(pw1.bias), _p(pw1.ln_cs), float(pw1.ln_eps), pw1.kpad, _p(pw2.wt), _p(pw2.bias), pw2.kpad, _p(residual),
+            _p(pw_p.wt), _p(pw_p.bias), pw_p.kpad, _p(x_in), _p(out), gnp, int(gn_cpg if gn is not None else 0), int(rows_per_batch), M, Cn, pw2.K,
+            _p(_zero_page(x2d.device)))
     if gn is not None:
         gn.attach(out)
     return out
@@ -644,10 +656,9 @@ def xattn_fused(x2d: torch.Tensor, pw_q: PackedWeight, k: torch.Tensor, vt: torc
         _chk_f16(residual, "xattn_fused.residual")
         assert residual.shape == x2d.shape
     _pf_note(pw_q.wt, pw_o.wt)
-    rc = _lib.lib().af_xattn_fused(_p(x2d), _p(pw_q.wt), _p(pw_q.bias), _p(pw_q.ln_cs), float(pw_q.ln_eps), pw_q.kpad, _p(k), int(ldk), _p(vt), int(vt.stride(0)),
-                                   int(vt.stride(1)), _p(pw_o.wt), _p(pw_o.bias), pw_o.kpad, _p(residual), _p(out), B, N, L, Cn, heads, float(scale),
-                                   _zero_page(x2d.device).data_ptr(), _stream())
-    _lib.check(rc, "af_xattn_fused")
+    _launch("af_xattn_fused", _p(x2d), _p(pw_q.wt), _p(pw_q.bias), _p(pw_q.ln_cs), float(pw_q.ln_eps), pw_q.kpad, _p(k), int(ldk), _p(vt), int(vt.stride(0)),
+            int(vt.stride(1)), _p(pw_o.wt), _p(pw_o.bias), pw_o.kpad, _p(residual), _p(out), B, N, L, Cn, heads, float(scale),
+            _zero_page(x2d.device).data_ptr())
     return out
 
 
@@ -663,10 +674,9 @@ def xattn_chain(ao: torch.Tensor, pw_o1: PackedWeight, x0: torch.Tensor, pw_q: P
     x1 = torch.empty_like(ao)
     out = torch.empty_like(ao)
     _pf_note(pw_o1.wt, pw_q.wt, pw_o.wt)
-    rc = _lib.lib().af_xattn_chain(_p(ao), _p(pw_o1.wt), _p(pw_o1.bias), pw_o1.kpad, _p(x0), _p(x1), _p(pw_q.wt), _p(pw_q.bias), _p(pw_q.ln_cs), float(pw_q.ln_eps),
-                                   pw_q.kpad, _p(k), int(ldk), _p(vt), int(vt.stride(0)), int(vt.stride(1)), _p(pw_o.wt), _p(pw_o.bias), pw_o.kpad, _p(out), B, N, L, Cn,
-                                   heads, float(scale), _zero_page(ao.device).data_ptr(), _stream())
-    _lib.check(rc, "af_xattn_chain")
+    _launch("af_xattn_chain", _p(ao), _p(pw_o1.wt), _p(pw_o1.bias), pw_o1.kpad, _p(x0), _p(x1), _p(pw_q.wt), _p(pw_q.bias), _p(pw_q.ln_cs), float(pw_q.ln_eps),
+            pw_q.kpad, _p(k), int(ldk), _p(vt), int(vt.stride(0)), int(vt.stride(1)), _p(pw_o.wt), _p(pw_o.bias), pw_o.kpad, _p(out), B, N, L, Cn,
+            heads, float(scale), _zero_page(ao.device).data_ptr())
     return out
 
 
@@ -702,16 +712,13 @@ def _groupnorm(x, gamma, beta, eps, silu, x2, groups, want_stats: bool):
     gn = partials_of(x) if x2 is None else None
     if gn is not None and gn.B == B and gn.hw == hw and gn.C == c1 and gn.cpg * groups == c1 and x.is_contiguous():
         # the launch that produced x left its partial statistics: normalise in one pass, no statistics pass (af_groupnorm_apply)
-        rc = _lib.lib().af_groupnorm_apply(_p(x), c1, _p(gamma), _p(beta), _p(y), _p(stats), B, hw, groups, float(eps), int(silu), _p(gn.ws), gn.nblk, _stream())
-        _lib.check(rc, "af_groupnorm_apply")
+        _launch("af_groupnorm_apply", _p(x), c1, _p(gamma), _p(beta), _p(y), _p(stats), B, hw, groups, float(eps), int(silu), _p(gn.ws), gn.nblk)
         return y, stats
     ws = _gn_workspace(x.device, B)
     if stats is None:
-        rc = _lib.lib().af_groupnorm(_p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(y), B, hw, groups, float(eps), int(silu), _p(ws), _stream())
-        _lib.check(rc, "af_groupnorm")
+        _launch("af_groupnorm", _p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(y), B, hw, groups, float(eps), int(silu), _p(ws))
     else:
-        rc = _lib.lib().af_groupnorm_stats(_p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(y), _p(stats), B, hw, groups, float(eps), int(silu), _p(ws), _stream())
-        _lib.check(rc, "af_groupnorm_stats")
+        _launch("af_groupnorm_stats", _p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(y), _p(stats), B, hw, groups, float(eps), int(silu), _p(ws))
     return y, stats
 
 
@@ -739,9 +746,8 @@ def gn_proj_fused(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
     _chk_f16(x, "gn_proj_fused.x")
     out = torch.empty((B * hw, pw.N), dtype=F16, device=x.device)
     _pf_note(pw.wt)
-    rc = _lib.lib().af_gn_proj_fused(_p(x), _p(gn.ws), gn.nblk, _p(gamma), _p(beta), float(eps), _p(pw.wt), _p(pw.bias), pw.kpad, _p(out), B, hw, c, groups,
-                                     _zero_page(x.device).data_ptr(), _stream())
-    _lib.check(rc, "af_gn_proj_fused")
+    _launch("af_gn_proj_fused", _p(x), _p(gn.ws), gn.nblk, _p(gamma), _p(beta), float(eps), _p(pw.wt), _p(pw.bias), pw.kpad, _p(out), B, hw, c, groups,
+            _zero_page(x.device).data_ptr())
     return out
 
 
@@ -749,8 +755,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     _chk_f16(x, "layernorm.x")
     Cn = x.shape[-1]
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().af_layernorm(_p(x), _p(gamma), _p(beta), _p(y), x.numel() // Cn, Cn, float(eps), _stream()),
-               "af_layernorm")
+    _launch("af_layernorm", _p(x), _p(gamma), _p(beta), _p(y), x.numel() // Cn, Cn, float(eps))
     return y
 
 
@@ -765,10 +770,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, *, B: int, Nq:
     scale = d ** -0.5 if scale is None else scale
     ldb = 0 if keybias is None else keybias.stride(0)
     lse = torch.empty((B, heads, round_up(Nq, 32)), dtype=torch.float32, device=q.device) if want_lse else None
-    rc = _lib.lib().af_attention_strided(_p(q), _p(k), _p(vt), _p(o), _p(lse), 0 if lse is None else lse.stride(1), _p(keybias),
-                                         int(causal_m), B, Nq, L, heads, d, ldq, ldk, Cn, vt.stride(1), ldb, vt.stride(0), float(scale),
-                                         _stream())
-    _lib.check(rc, "af_attention")
+    _launch("af_attention_strided", _p(q), _p(k), _p(vt), _p(o), _p(lse), 0 if lse is None else lse.stride(1), _p(keybias),
+            int(causal_m), B, Nq, L, heads, d, ldq, ldk, Cn, vt.stride(1), ldb, vt.stride(0), float(scale))
     return (o, lse) if want_lse else o
 
 
@@ -785,10 +788,8 @@ def attention_bwd(q, k, v, o, dout, lse, *, B: int, Nq: int, L: int, heads: int,
     need = _lib.lib().af_attention_bwd_scratch_bytes(B, Nq, L, heads, d)
     sc = _grow_scratch(_attn_scratch, q.device, need, torch.uint8, floor=64 << 20)
     ldb = 0 if keybias is None else keybias.stride(0)
-    rc = _lib.lib().af_attention_bwd(_p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), lse.stride(1), _p(keybias), int(causal_m), _p(dq), _p(dk),
-                                     _p(dv), _p(sc), sc.numel(), B, Nq, L, heads, d, ldq, ldk, ldv, Cn, Cn, lddq, lddk, lddv,
-                                     ldb, float(scale), _stream())
-    _lib.check(rc, "af_attention_bwd")
+    _launch("af_attention_bwd", _p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), lse.stride(1), _p(keybias), int(causal_m), _p(dq), _p(dk),
+            _p(dv), _p(sc), sc.numel(), B, Nq, L, heads, d, ldq, ldk, ldv, Cn, Cn, lddq, lddk, lddv, ldb, float(scale))
 
 
 def attention_scores(q: torch.Tensor, k: torch.Tensor, *, B: int, Nq: int, L: int, heads: int, d: int,
@@ -799,8 +800,7 @@ def attention_scores(q: torch.Tensor, k: torch.Tensor, *, B: int, Nq: int, L: in
     score = torch.empty((B, heads, Nq, L), dtype=torch.float32, device=q.device)
     prob = torch.empty_like(score)
     scale = d ** -0.5 if scale is None else scale
-    _lib.check(_lib.lib().af_attention_scores(_p(q), _p(k), _p(score), _p(prob), B, Nq, L, heads, d, float(scale), _stream()),
-               "af_attention_scores")
+    _launch("af_attention_scores", _p(q), _p(k), _p(score), _p(prob), B, Nq, L, heads, d, float(scale))
     return score, prob
 
 
@@ -821,7 +821,7 @@ def xattn_scores(q, k, *, B, Nq, L, heads, d, scale):
     _chk_f16_rows(q, "xattn_scores.q")
     _chk_f16_rows(k, "xattn_scores.k")
     score = torch.empty((B, heads, Nq, L), dtype=torch.float32, device=q.device)
-    _lib.check(_lib.lib().af_xattn_scores(_p(q), _ld(q), _p(k), _ld(k), _p(score), B, Nq, L, heads, d, float(scale), _stream()), "af_xattn_scores")
+    _launch("af_xattn_scores", _p(q), _ld(q), _p(k), _ld(k), _p(score), B, Nq, L, heads, d, float(scale))
     return score
 
 
@@ -831,7 +831,7 @@ def xattn_softmax_pv(score, v, *, B, Nq, L, heads, d):
     assert score.dtype == torch.float32 and score.is_contiguous() and tuple(score.shape) == (B, heads, Nq, L)
     prob = torch.empty_like(score)
     o = torch.empty((B * Nq, heads * d), dtype=F16, device=v.device)
-    _lib.check(_lib.lib().af_xattn_softmax_pv(_p(score), _p(v), _ld(v), _p(prob), _p(o), heads * d, B, Nq, L, heads, d, _stream()), "af_xattn_softmax_pv")
+    _launch("af_xattn_softmax_pv", _p(score), _p(v), _ld(v), _p(prob), _p(o), heads * d, B, Nq, L, heads, d)
     return prob, o
 
 
@@ -841,15 +841,14 @@ def xattn_softmax_pv_bwd(prob, v, dout, dprob_ext, *, B, Nq, L, heads, d):
     dscore = torch.empty_like(prob)
     if dprob_ext is not None:
         dprob_ext = dprob_ext.to(torch.float32).contiguous()
-    _lib.check(_lib.lib().af_xattn_softmax_pv_bwd(_p(prob), _p(v), _ld(v), _p(dout), _ld(dout), _p(dprob_ext), _p(dscore), B, Nq, L, heads, d,
-                                                  _stream()), "af_xattn_softmax_pv_bwd")
+    _launch("af_xattn_softmax_pv_bwd", _p(prob), _p(v), _ld(v), _p(dout), _ld(dout), _p(dprob_ext), _p(dscore), B, Nq, L, heads, d)
     return dscore
 
 
 def xattn_rowmix(w, x, alpha, *, B, Nq, L, heads, d):
     """out fp16 [B*Nq, heads*d] = alpha * w x  (w fp32 [B, heads, Nq, L], x fp16 [B*L, >=C])."""
     out = torch.empty((B * Nq, heads * d), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_xattn_rowmix(_p(w), _p(x), _ld(x), _p(out), heads * d, float(alpha), B, Nq, L, heads, d, _stream()), "af_xattn_rowmix")
+    _launch("af_xattn_rowmix", _p(w), _p(x), _ld(x), _p(out), heads * d, float(alpha), B, Nq, L, heads, d)
     return out
 
 
@@ -858,8 +857,7 @@ def xattn_colmix(w, x, alpha, *, B, Nq, L, heads, d):
     out = torch.empty((B * L, heads * d), dtype=F16, device=x.device)
     nb = int(_lib.lib().af_xattn_colmix_ws_bytes(B, L, heads, d))
     ws = torch.empty((nb // 4,), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().af_xattn_colmix(_p(w), _p(x), _ld(x), _p(out), heads * d, float(alpha), _p(ws), nb, B, Nq, L, heads, d, _stream()),
-               "af_xattn_colmix")
+    _launch("af_xattn_colmix", _p(w), _p(x), _ld(x), _p(out), heads * d, float(alpha), _p(ws), nb, B, Nq, L, heads, d)
     return out
 
 
@@ -876,8 +874,7 @@ def make_keybias(mask: torch.Tensor, L: int) -> torch.Tensor:
 def timestep_embedding(timesteps: torch.Tensor, dim: int, max_period: float = 10000.0) -> torch.Tensor:
     t = timesteps.to(dtype=torch.int64).contiguous()
     out = torch.empty((t.shape[0], dim), dtype=F16, device=t.device)
-    _lib.check(_lib.lib().af_timestep_embedding(_p(t), _p(out), t.shape[0], dim, float(max_period), _stream()),
-               "af_timestep_embedding")
+    _launch("af_timestep_embedding", _p(t), _p(out), t.shape[0], dim, float(max_period))
     return out
 
 
@@ -886,7 +883,7 @@ def nchw_f32_to_nhwc_f16(x: torch.Tensor, cpad: int = 0) -> torch.Tensor:
     B, Cn, H, W = x.shape
     cpad = max(cpad, Cn)
     y = torch.empty((B, H, W, cpad), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_nchw_f32_to_nhwc_f16(_p(x), _p(y), B, Cn, H * W, cpad, _stream()), "af_nchw_f32_to_nhwc_f16")
+    _launch("af_nchw_f32_to_nhwc_f16", _p(x), _p(y), B, Cn, H * W, cpad)
     return y
 
 
@@ -895,14 +892,14 @@ def nhwc_f16_to_nchw_f32(x: torch.Tensor, Cn: Optional[int] = None) -> torch.Ten
     B, H, W, cs = x.shape
     Cn = Cn or cs
     y = torch.empty((B, Cn, H, W), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().af_nhwc_f16_to_nchw_f32(_p(x), _p(y), B, Cn, H * W, cs, _stream()), "af_nhwc_f16_to_nchw_f32")
+    _launch("af_nhwc_f16_to_nchw_f32", _p(x), _p(y), B, Cn, H * W, cs)
     return y
 
 
 def silu(x: torch.Tensor) -> torch.Tensor:
     _chk_f16(x, "silu.x")
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().af_silu_f16(_p(x), _p(y), x.numel(), _stream()), "af_silu_f16")
+    _launch("af_silu_f16", _p(x), _p(y), x.numel())
     return y
 
 
@@ -910,7 +907,7 @@ def gelu(x: torch.Tensor) -> torch.Tensor:
     """erf-GELU, fp16 (af_gelu_f16): the MLP activation of DINO's ViT."""
     _chk_f16(x, "gelu.x")
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().af_gelu_f16(_p(x), _p(y), x.numel(), _stream()), "af_gelu_f16")
+    _launch("af_gelu_f16", _p(x), _p(y), x.numel())
     return y
 
 
@@ -949,8 +946,7 @@ def vit_patch_rows(images_u8: torch.Tensor, *, keep_aspect: bool, S: int, C: int
     kpad = kpad or round_up(3 * p * p, 64)
     rows = torch.empty((B * (C // max(p, 1)) ** 2, kpad), dtype=F16, device=images_u8.device)
     scale, shift = _vit_affine(tuple(mean), tuple(std))
-    _lib.check(_lib.lib().af_vit_patch_rows(_p(images_u8), _p(rows), B, H, W, int(bool(keep_aspect)), int(S), int(C), int(p), VIT_FILTERS[filter],
-                                            scale, shift, kpad, _stream()), "af_vit_patch_rows")
+    _launch("af_vit_patch_rows", _p(images_u8), _p(rows), B, H, W, int(bool(keep_aspect)), int(S), int(C), int(p), VIT_FILTERS[filter], scale, shift, kpad)
     return rows
 
 
@@ -995,7 +991,7 @@ def _cfg_step(kind: str, eps2: torch.Tensor, x: torch.Tensor, inputs, scalars, h
     name = f"af_cfg_{kind}_step" if blend is None else f"af_cfg_{kind}_inpaint_step"
     args = [_p(eps2), _p(x), *(None if t is None else _p(t) for t in inputs), _p(out), _p(aux), n, int(has_uncond),
             *(float(v) for v in scalars), *(() if blend is None else blend.args(x))]
-    _lib.check(getattr(_lib.lib(), name)(*args, _stream()), name)
+    _launch(name, *args)
     return out, aux
 
 
@@ -1034,7 +1030,7 @@ def q_sample(x0: torch.Tensor, noise: torch.Tensor, sa: torch.Tensor, sb: torch.
     sa, sb = sa.to(torch.float32).contiguous(), sb.to(torch.float32).contiguous()
     B = x0.shape[0]
     xt = torch.empty_like(x0)
-    _lib.check(_lib.lib().af_q_sample(_p(x0), _p(noise), _p(sa), _p(sb), _p(xt), B, x0.numel() // B, _stream()), "af_q_sample")
+    _launch("af_q_sample", _p(x0), _p(noise), _p(sa), _p(sb), _p(xt), B, x0.numel() // B)
     return xt
 
 
@@ -1046,7 +1042,7 @@ def image_u8_to_nhwc_f16(img_u8: torch.Tensor) -> torch.Tensor:
         raise RuntimeError(f"image_u8_to_nhwc_f16: expected [B, H, W, 3], got {tuple(img_u8.shape)}")
     B, H, W, _ = img_u8.shape
     out = torch.empty((B, H, W, 8), dtype=F16, device=img_u8.device)
-    _lib.check(_lib.lib().af_image_u8_to_nhwc_f16(_p(img_u8), _p(out), B, H, W, _stream()), "af_image_u8_to_nhwc_f16")
+    _launch("af_image_u8_to_nhwc_f16", _p(img_u8), _p(out), B, H, W)
     return out
 
 
@@ -1070,10 +1066,10 @@ def vae_latents_q_sample(h: torch.Tensor, qw: torch.Tensor, qb: torch.Tensor, n_
     x_t = torch.empty((out_count, 4, hh, ww), dtype=torch.float32, device=h.device)
     args = [_p(h), _p(qw), _p(qb), _p(n_post), _p(n_fwd), float(scale), float(sa), float(sb), _p(x_t)]
     if not with_z:
-        _lib.check(_lib.lib().af_vae_latents_q_sample(*args, B_img, out_count, hh, ww, _stream()), "af_vae_latents_q_sample")
+        _launch("af_vae_latents_q_sample", *args, B_img, out_count, hh, ww)
         return x_t
     z = torch.empty((B_img, 4, hh, ww), dtype=torch.float32, device=h.device)
-    _lib.check(_lib.lib().af_vae_latents_z_q_sample(*args, _p(z), B_img, out_count, hh, ww, _stream()), "af_vae_latents_z_q_sample")
+    _launch("af_vae_latents_z_q_sample", *args, _p(z), B_img, out_count, hh, ww)
     return x_t, z
 
 
@@ -1099,9 +1095,7 @@ def latent_resize_q_sample(x: torch.Tensor, size_hw, mode: str = "bilinear", noi
         raise RuntimeError(f"latent_resize_q_sample.noise: expected contiguous fp32 {(B, Cn, H, W)} on {x.device}, got {noise.dtype} "
                            f"{tuple(noise.shape)} on {noise.device}")
     out = torch.empty((B, Cn, H, W), dtype=torch.float32, device=x.device)
-    rc = _lib.lib().af_latent_resize_q_sample(_p(x), _p(noise), _p(out), B * Cn, h, w, H, W, RESIZE_MODES[mode], float(sa), float(sb),
-                                              _stream())
-    _lib.check(rc, "af_latent_resize_q_sample")
+    _launch("af_latent_resize_q_sample", _p(x), _p(noise), _p(out), B * Cn, h, w, H, W, RESIZE_MODES[mode], float(sa), float(sb))
     return out
 
 
@@ -1114,17 +1108,15 @@ def groupnorm_bwd(x, gamma, beta, stats, dy, silu, *, x2=None, add=None, groups=
     _chk_f16(dy, "groupnorm_bwd.dy")
     dx1 = torch.empty_like(x)
     dx2 = None if x2 is None else torch.empty_like(x2)
-    rc = _lib.lib().af_groupnorm_bwd(_p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(stats), _p(dy), _p(add), _p(dx1), _p(dx2), B,
-                                     hw, groups, int(silu), _p(_gn_workspace(x.device, B)), _stream())
-    _lib.check(rc, "af_groupnorm_bwd")
+    _launch("af_groupnorm_bwd", _p(x), _p(x2), c1, c2, _p(gamma), _p(beta), _p(stats), _p(dy), _p(add), _p(dx1), _p(dx2), B,
+            hw, groups, int(silu), _p(_gn_workspace(x.device, B)))
     return dx1 if x2 is None else (dx1, dx2)
 
 
 def layernorm_bwd(x, gamma, dy, eps=1e-5, add=None):
     dx = torch.empty_like(x)
     Cn = x.shape[-1]
-    _lib.check(_lib.lib().af_layernorm_bwd(_p(x), _p(gamma), _p(dy), _p(add), _p(dx), x.numel() // Cn, Cn, float(eps), _stream()),
-               "af_layernorm_bwd")
+    _launch("af_layernorm_bwd", _p(x), _p(gamma), _p(dy), _p(add), _p(dx), x.numel() // Cn, Cn, float(eps))
     return dx
 
 
@@ -1134,28 +1126,27 @@ def layernorm_param_grads(x, dy, eps=1e-5):
     rows = x.numel() // Cn
     out = torch.empty((2 * Cn + 2 * rows,), dtype=torch.float32, device=x.device)        # dgamma | dbeta | row statistics scratch
     dg, db, st = out[:Cn], out[Cn:2 * Cn], out[2 * Cn:]
-    _lib.check(_lib.lib().af_layernorm_param_grads(_p(x), _p(dy), _p(dg), _p(db), _p(st), rows, Cn, float(eps), _stream()),
-               "af_layernorm_param_grads")
+    _launch("af_layernorm_param_grads", _p(x), _p(dy), _p(dg), _p(db), _p(st), rows, Cn, float(eps))
     return dg, db
 
 
 def geglu_fwd(hp):
     M, two_i = hp.shape
     out = torch.empty((M, two_i // 2), dtype=F16, device=hp.device)
-    _lib.check(_lib.lib().af_geglu_fwd(_p(hp), _p(out), M, two_i // 2, _stream()), "af_geglu_fwd")
+    _launch("af_geglu_fwd", _p(hp), _p(out), M, two_i // 2)
     return out
 
 
 def geglu_bwd(hp, dout):
     dhp = torch.empty_like(hp)
-    _lib.check(_lib.lib().af_geglu_bwd(_p(hp), _p(dout), _p(dhp), hp.shape[0], hp.shape[1] // 2, _stream()), "af_geglu_bwd")
+    _launch("af_geglu_bwd", _p(hp), _p(dout), _p(dhp), hp.shape[0], hp.shape[1] // 2)
     return dhp
 
 
 def sumpool2x2(x):
     B, H2, W2, Cn = x.shape
     y = torch.empty((B, H2 // 2, W2 // 2, Cn), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_sumpool2x2(_p(x), _p(y), B, H2 // 2, W2 // 2, Cn, _stream()), "af_sumpool2x2")
+    _launch("af_sumpool2x2", _p(x), _p(y), B, H2 // 2, W2 // 2, Cn)
     return y
 
 
@@ -1164,7 +1155,7 @@ def add(a, b):
     _chk_f16(b, "add.b")
     assert a.shape == b.shape
     out = torch.empty_like(a)
-    _lib.check(_lib.lib().af_add_f16(_p(a), _p(b), _p(out), a.numel(), _stream()), "af_add_f16")
+    _launch("af_add_f16", _p(a), _p(b), _p(out), a.numel())
     return out
 
 
@@ -1174,7 +1165,7 @@ def axpy(a, b, alpha):
     _chk_f16(b, "axpy.b")
     assert a.shape == b.shape
     out = torch.empty_like(a)
-    _lib.check(_lib.lib().af_axpy_f16(_p(a), _p(b), float(alpha), _p(out), a.numel(), _stream()), "af_axpy_f16")
+    _launch("af_axpy_f16", _p(a), _p(b), float(alpha), _p(out), a.numel())
     return out
 
 
@@ -1182,7 +1173,7 @@ def transpose_tokens(x, B, N, Cn, ldx):
     """x: rows of a [B*N, ldx] token tensor (Cn columns from x's first column) -> [B, Cn, roundup(N, 8)]."""
     ldy = round_up(N, 8)
     y = torch.empty((B, Cn, ldy), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_transpose_tokens(_p(x), _p(y), B, N, Cn, ldx, ldy, _stream()), "af_transpose_tokens")
+    _launch("af_transpose_tokens", _p(x), _p(y), B, N, Cn, ldx, ldy)
     return y
 
 
@@ -1190,10 +1181,8 @@ def cadamw_step(p, g, m, v, seg_offsets, counts, *, lr, betas=(0.9, 0.999), eps=
     """Fused cautious-AdamW step (c_adamw.py:65-123) on flat fp32 buffers; seg_offsets int64 [nseg+1] on the device."""
     for t in (p, g, m, v):
         assert t.dtype == torch.float32 and t.is_contiguous()
-    rc = _lib.lib().af_cadamw_step(_p(p), _p(g), _p(m), _p(v), _p(seg_offsets), seg_offsets.numel() - 1, _p(counts), float(lr),
-                                   float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), int(correct_bias),
-                                   _stream())
-    _lib.check(rc, "af_cadamw_step")
+    _launch("af_cadamw_step", _p(p), _p(g), _p(m), _p(v), _p(seg_offsets), seg_offsets.numel() - 1, _p(counts), float(lr),
+            float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), int(correct_bias))
 
 
 def colsum(a, b=None, out=None, accumulate=False):
@@ -1204,31 +1193,31 @@ def colsum(a, b=None, out=None, accumulate=False):
     if rows >= 2048:                                           # tall: spread the rows over workgroups (two deterministic passes)
         chunks = min(256, (rows + 255) // 256)
         partial = torch.empty((chunks, Cn), dtype=torch.float32, device=a.device)
-        _lib.check(_lib.lib().af_colsum_tall(_p(a), _p(b), _p(partial), _p(out), rows, Cn, chunks, int(accumulate), _stream()), "af_colsum_tall")
+        _launch("af_colsum_tall", _p(a), _p(b), _p(partial), _p(out), rows, Cn, chunks, int(accumulate))
         return out
-    _lib.check(_lib.lib().af_colsum(_p(a), _p(b), _p(out), rows, Cn, int(accumulate), _stream()), "af_colsum")
+    _launch("af_colsum", _p(a), _p(b), _p(out), rows, Cn, int(accumulate))
     return out
 
 
 def quickgelu_fwd(x):
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().af_quickgelu_fwd(_p(x), _p(y), x.numel(), _stream()), "af_quickgelu_fwd")
+    _launch("af_quickgelu_fwd", _p(x), _p(y), x.numel())
     return y
 
 
 def quickgelu_bwd(x, dy):
     dx = torch.empty_like(x)
-    _lib.check(_lib.lib().af_quickgelu_bwd(_p(x), _p(dy), _p(dx), x.numel(), _stream()), "af_quickgelu_bwd")
+    _launch("af_quickgelu_bwd", _p(x), _p(dy), _p(dx), x.numel())
     return dx
 
 
 def clamp_f32_(a, lo, hi):
-    _lib.check(_lib.lib().af_clamp_f32(_p(a), float(lo), float(hi), a.numel(), _stream()), "af_clamp_f32")
+    _launch("af_clamp_f32", _p(a), float(lo), float(hi), a.numel())
     return a
 
 
 def scale_f32_(a, s):
-    _lib.check(_lib.lib().af_scale_f32(_p(a), float(s), a.numel(), _stream()), "af_scale_f32")
+    _launch("af_scale_f32", _p(a), float(s), a.numel())
     return a
 
 
@@ -1237,7 +1226,7 @@ def softmax_rows(x):
     _chk_f16(x, "softmax_rows.x")
     rows, L = x.shape
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().af_softmax_rows(_p(x), _p(y), rows, L, _stream()), "af_softmax_rows")
+    _launch("af_softmax_rows", _p(x), _p(y), rows, L)
     return y
 
 
@@ -1255,8 +1244,7 @@ def vae_attention(q, k, v, *, B: int, N: int, C: int):
             raise RuntimeError(f"vae_attention.{name}: expected [{B * N}, {C}], got {tuple(t.shape)}")
     vt = transpose_tokens(v, B, N, C, _ld(v))
     o = torch.empty((B * N, C), dtype=F16, device=q.device)
-    rc = _lib.lib().af_vae_attention(_p(q), _p(k), _p(vt), _p(o), B, N, C, _ld(q), _ld(k), vt.stride(1), C, _stream())
-    _lib.check(rc, "af_vae_attention")
+    _launch("af_vae_attention", _p(q), _p(k), _p(vt), _p(o), B, N, C, _ld(q), _ld(k), vt.stride(1), C)
     return o
 
 
@@ -1271,8 +1259,7 @@ def temporal_attention(qkv, *, B: int, F: int, HW: int, heads: int, d: int, scal
     if qkv.shape[0] != B * F * HW or qkv.shape[1] < 3 * Cn:
         raise RuntimeError(f"temporal_attention.qkv: expected [{B * F * HW}, >= {3 * Cn}], got {tuple(qkv.shape)}")
     o = torch.empty((B * F * HW, Cn), dtype=F16, device=qkv.device)
-    rc = _lib.lib().af_temporal_attention(_p(qkv), _ld(qkv), _p(o), B, F, HW, heads, d, float(d ** -0.5 if scale is None else scale), _stream())
-    _lib.check(rc, "af_temporal_attention")
+    _launch("af_temporal_attention", _p(qkv), _ld(qkv), _p(o), B, F, HW, heads, d, float(d ** -0.5 if scale is None else scale))
     return o
 
 
@@ -1282,14 +1269,14 @@ def softmax_rows_bwd(p, dp):
     _chk_f16(dp, "softmax_rows_bwd.dp")
     assert p.shape == dp.shape
     ds = torch.empty_like(p)
-    _lib.check(_lib.lib().af_softmax_rows_bwd(_p(p), _p(dp), _p(ds), p.shape[0], p.shape[1], _stream()), "af_softmax_rows_bwd")
+    _launch("af_softmax_rows_bwd", _p(p), _p(dp), _p(ds), p.shape[0], p.shape[1])
     return ds
 
 
 def mask_pairs_(p, cls):
     """In place: p [N, N] fp16 *= ((cls[i] & cls[j]) != 0); cls uint8 [N] (bit 0 foreground, bit 1 background)."""
     assert p.shape[0] == p.shape[1] == cls.numel() and cls.dtype == torch.uint8
-    _lib.check(_lib.lib().af_mask_pairs(_p(p), _p(cls), p.shape[0], _stream()), "af_mask_pairs")
+    _launch("af_mask_pairs", _p(p), _p(cls), p.shape[0])
     return p
 
 
@@ -1298,7 +1285,7 @@ def dora_combine(y0, c2, lb, u, v):
     """y0 + u[c] * c2 + v[c] * lb over the last (channel) axis; u, v fp32 [C]."""
     Cn = y0.shape[-1]
     out = torch.empty_like(y0)
-    _lib.check(_lib.lib().af_dora_combine(_p(y0), _p(c2), _p(lb), _p(u), _p(v), _p(out), y0.numel() // Cn, Cn, _stream()), "af_dora_combine")
+    _launch("af_dora_combine", _p(y0), _p(c2), _p(lb), _p(u), _p(v), _p(out), y0.numel() // Cn, Cn)
     return out
 
 
@@ -1307,7 +1294,7 @@ def mul(a, b):
     _chk_f16(b, "mul.b")
     assert a.shape == b.shape
     out = torch.empty_like(a)
-    _lib.check(_lib.lib().af_mul_f16(_p(a), _p(b), _p(out), a.numel(), _stream()), "af_mul_f16")
+    _launch("af_mul_f16", _p(a), _p(b), _p(out), a.numel())
     return out
 
 
@@ -1316,7 +1303,7 @@ def im2col3x3(x, stride=1):
     B, H, W, Cn = x.shape
     Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
     out = torch.empty((B * Ho * Wo, 9 * Cn), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_im2col3x3(_p(x), _p(out), B, H, W, Cn, stride, _stream()), "af_im2col3x3")
+    _launch("af_im2col3x3", _p(x), _p(out), B, H, W, Cn, stride)
     return out
 
 
@@ -1325,7 +1312,7 @@ def affine_prelu(x, scale=None, shift=None, slope=None):
     """y = prelu(x * scale[c] + shift[c]) over the last (channel) axis; any of the two stages may be absent."""
     Cn = x.shape[-1]
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().af_affine_prelu(_p(x), _p(scale), _p(shift), _p(slope), _p(y), x.numel() // Cn, Cn, _stream()), "af_affine_prelu")
+    _launch("af_affine_prelu", _p(x), _p(scale), _p(shift), _p(slope), _p(y), x.numel() // Cn, Cn)
     return y
 
 
@@ -1338,8 +1325,7 @@ def affine_prelu_ch(x, scale=None, shift=None, slope=None):
             raise RuntimeError(f"affine_prelu_ch.{name}: expected contiguous fp32 ({Cn},) on {x.device}, got {t.dtype} {tuple(t.shape)} "
                                f"on {t.device}")
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().af_affine_prelu_ch(_p(x), _p(scale), _p(shift), _p(slope), _p(y), x.numel() // Cn, Cn, _stream()),
-               "af_affine_prelu_ch")
+    _launch("af_affine_prelu_ch", _p(x), _p(scale), _p(shift), _p(slope), _p(y), x.numel() // Cn, Cn)
     return y
 
 
@@ -1361,7 +1347,7 @@ def face_align_crop(image_u8, inv_mats, size=112):
     if size not in (112, 128):                       # (before the allocation: the C ABI refuses it too)
         raise RuntimeError(f"face_align_crop: size must be 112 or 128, got {size}")
     out = torch.empty((nf, size, size, 8), dtype=F16, device=image_u8.device)
-    _lib.check(_lib.lib().af_face_align_crop(_p(image_u8), _p(inv_mats), _p(out), H, W, nf, size, _stream()), "af_face_align_crop")
+    _launch("af_face_align_crop", _p(image_u8), _p(inv_mats), _p(out), H, W, nf, size)
     return out
 
 
@@ -1379,7 +1365,7 @@ def face_align_crop_any(image_u8, inv_mats, size):
     if size < 8 or size > 1024 or size % 8:
         raise RuntimeError(f"face_align_crop_any: size must be a multiple of 8 from 8 to 1024, got {size}")
     out = torch.empty((nf, size, size, 8), dtype=F16, device=image_u8.device)
-    _lib.check(_lib.lib().af_face_align_crop_any(_p(image_u8), _p(inv_mats), _p(out), H, W, nf, size, _stream()), "af_face_align_crop_any")
+    _launch("af_face_align_crop_any", _p(image_u8), _p(inv_mats), _p(out), H, W, nf, size)
     return out
 
 
@@ -1402,8 +1388,7 @@ def modulate_weights(w, wsq, styles, out, gain=1.0):
     _chk_f16(out, "modulate_weights.out")
     if out.dim() != 3 or out.shape[0] != B:
         raise RuntimeError(f"modulate_weights.out: expected [{B}, npad, kpad], got {tuple(out.shape)}")
-    _lib.check(_lib.lib().af_modulate_weights(_p(w), _p(wsq), _p(styles), _p(out), B, cout, cin, taps, out.shape[1], out.shape[2],
-                                              int(wsq is not None), float(gain), _stream()), "af_modulate_weights")
+    _launch("af_modulate_weights", _p(w), _p(wsq), _p(styles), _p(out), B, cout, cin, taps, out.shape[1], out.shape[2], int(wsq is not None), float(gain))
     return out
 
 
@@ -1433,8 +1418,7 @@ def style_epilogue(y, noise=None, bias=None, scale=None, shift=None, nw=0.0, out
     else:
         _chk_f16(out, "style_epilogue.out")
         assert out.shape == y.shape
-    _lib.check(_lib.lib().af_style_epilogue(_p(y), _p(noise), _p(bias), _p(scale), _p(shift), _p(out), B, hw, Cn, float(nw), _stream()),
-               "af_style_epilogue")
+    _launch("af_style_epilogue", _p(y), _p(noise), _p(bias), _p(scale), _p(shift), _p(out), B, hw, Cn, float(nw))
     return out
 
 
@@ -1447,7 +1431,7 @@ def bilinear_up2(x, addend=None):
         _chk_f16(addend, "bilinear_up2.addend")
         if addend.shape != out.shape:
             raise RuntimeError(f"bilinear_up2.addend: expected {tuple(out.shape)}, got {tuple(addend.shape)}")
-    _lib.check(_lib.lib().af_bilinear_up2(_p(x), _p(addend), _p(out), B, H, W, Cn, _stream()), "af_bilinear_up2")
+    _launch("af_bilinear_up2", _p(x), _p(addend), _p(out), B, H, W, Cn)
     return out
 
 
@@ -1465,8 +1449,8 @@ def face_paste_affine_u8(photo_u8, crops, mats, erode, feather):
             raise RuntimeError(f"face_paste_affine_u8.crops: expected [F, S, S, ld] on {photo_u8.device}, got {tuple(crops.shape)} on {crops.device}")
         _chk_f32(mats, (nf, 2, 3), "face_paste_affine_u8.mats", photo_u8.device)
         S, ld = crops.shape[1], crops.shape[3]
-    _lib.check(_lib.lib().af_face_paste_affine_u8(_p(photo_u8), _p(crops) if nf else None, _p(mats) if nf else None, _p(out), H, W, nf, S, ld,
-                                                  float(erode), float(feather), _stream()), "af_face_paste_affine_u8")
+    _launch("af_face_paste_affine_u8", _p(photo_u8), _p(crops) if nf else None, _p(mats) if nf else None, _p(out), H, W, nf, S, ld,
+            float(erode), float(feather))
     return out
 
 
@@ -1501,8 +1485,7 @@ def stem_im2col7x7(images_u8, scale, shift, bgr=False):
         raise RuntimeError(f"stem_im2col7x7: {tuple(images_u8.shape)} needs 2^31 bytes or more in one operand; split the batch")
     out = torch.empty((B * Ho * Wo, STEM_COLS), dtype=F16, device=images_u8.device)
     f3 = C.c_float * 3
-    _lib.check(_lib.lib().af_stem_im2col7x7(_p(images_u8), f3(*scale), f3(*shift), _p(out), B, H, W, int(bool(bgr)), _stream()),
-               "af_stem_im2col7x7")
+    _launch("af_stem_im2col7x7", _p(images_u8), f3(*scale), f3(*shift), _p(out), B, H, W, int(bool(bgr)))
     return out, (Ho, Wo)
 
 
@@ -1511,7 +1494,7 @@ def relu_maxpool3x3s2(x):
     _chk_nhwc(x, "relu_maxpool3x3s2.x")
     B, H, W, Cn = x.shape
     y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cn), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_relu_maxpool3x3s2(_p(x), _p(y), B, H, W, Cn, _stream()), "af_relu_maxpool3x3s2")
+    _launch("af_relu_maxpool3x3s2", _p(x), _p(y), B, H, W, Cn)
     return y
 
 
@@ -1520,7 +1503,7 @@ def subsample2x(x):
     _chk_nhwc(x, "subsample2x.x")
     B, H, W, Cn = x.shape
     y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, Cn), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_subsample2x(_p(x), _p(y), B, H, W, Cn, _stream()), "af_subsample2x")
+    _launch("af_subsample2x", _p(x), _p(y), B, H, W, Cn)
     return y
 
 
@@ -1532,7 +1515,7 @@ def upsample2x_add(a, b):
     if tuple(a.shape) != (B, 2 * h, 2 * w, Cn) or a.device != b.device:
         raise RuntimeError(f"upsample2x_add: a must be [B, 2h, 2w, C] for b {tuple(b.shape)} on {b.device}, got {tuple(a.shape)} on {a.device}")
     y = torch.empty_like(a)
-    _lib.check(_lib.lib().af_upsample2x_add(_p(a), _p(b), _p(y), B, h, w, Cn, _stream()), "af_upsample2x_add")
+    _launch("af_upsample2x_add", _p(a), _p(b), _p(y), B, h, w, Cn)
     return y
 
 
@@ -1555,8 +1538,7 @@ def retina_decode(heads, level_hw, conf_thr, capacity=RETINA_CAPACITY, steps=RET
     hw = (C.c_int * 6)(*[int(v) for pair in level_hw for v in pair])
     st = (C.c_int * 3)(*[int(v) for v in steps])
     ms = (C.c_float * 6)(*[float(v) for pair in min_sizes for v in pair])
-    _lib.check(_lib.lib().af_retina_decode(_p(heads[0]), _p(heads[1]), _p(heads[2]), hw, st, ms, B, float(conf_thr), _p(cand), _p(count),
-                                           capacity, _stream()), "af_retina_decode")
+    _launch("af_retina_decode", _p(heads[0]), _p(heads[1]), _p(heads[2]), hw, st, ms, B, float(conf_thr), _p(cand), _p(count), capacity)
     return cand, count
 
 
@@ -1574,8 +1556,7 @@ def retina_nms(cand, count, nms_thr, max_det=64):
         raise RuntimeError(f"retina_nms: needs 1 <= max_det <= capacity <= {RETINA_CAPACITY}, got max_det {max_det}, capacity {cap}")
     buf = torch.empty((B * max_det * 16 + B * 2,), dtype=torch.float32, device=cand.device)          # table | counts: one copy out
     table, counts = buf[:B * max_det * 16], buf[B * max_det * 16:]
-    _lib.check(_lib.lib().af_retina_nms(_p(cand), _p(count), _p(table), _p(counts), B, cap, max_det, float(nms_thr), _stream()),
-               "af_retina_nms")
+    _launch("af_retina_nms", _p(cand), _p(count), _p(table), _p(counts), B, cap, max_det, float(nms_thr))
     host = buf.cpu()
     table, counts = host[:B * max_det * 16].reshape(B, max_det, 16), host[B * max_det * 16:].view(torch.int32).reshape(B, 2)
     if int(counts[:, 1].max()) > cap:
@@ -1587,22 +1568,21 @@ def retina_nms(cand, count, nms_thr, max_det=64):
 def maxpool2x2(x):
     B, H2, W2, Cn = x.shape
     y = torch.empty((B, H2 // 2, W2 // 2, Cn), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_maxpool2x2(_p(x), _p(y), B, H2 // 2, W2 // 2, Cn, _stream()), "af_maxpool2x2")
+    _launch("af_maxpool2x2", _p(x), _p(y), B, H2 // 2, W2 // 2, Cn)
     return y
 
 
 def global_avgpool(x):
     B, H, W, Cn = x.shape
     out = torch.empty((B, Cn), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_global_avgpool(_p(x), _p(out), B, H * W, Cn, _stream()), "af_global_avgpool")
+    _launch("af_global_avgpool", _p(x), _p(out), B, H * W, Cn)
     return out
 
 
 def se_residual_prelu(x, se_logits, residual, slope):
     B, H, W, Cn = x.shape
     y = torch.empty_like(x)
-    _lib.check(_lib.lib().af_se_residual_prelu(_p(x), _p(se_logits), _p(residual), _p(slope), _p(y), B, H * W, Cn, _stream()),
-               "af_se_residual_prelu")
+    _launch("af_se_residual_prelu", _p(x), _p(se_logits), _p(residual), _p(slope), _p(y), B, H * W, Cn)
     return y
 
 
@@ -1611,8 +1591,7 @@ def affine_prelu_bwd(dy, x=None, scale=None, shift=None, slope=None):
     _chk_f16(dy, "affine_prelu_bwd.dy")
     Cn = dy.shape[-1]
     dx = torch.empty_like(dy)
-    _lib.check(_lib.lib().af_affine_prelu_bwd(_p(x), _p(scale), _p(shift), _p(slope), _p(dy), _p(dx), dy.numel() // Cn, Cn, _stream()),
-               "af_affine_prelu_bwd")
+    _launch("af_affine_prelu_bwd", _p(x), _p(scale), _p(shift), _p(slope), _p(dy), _p(dx), dy.numel() // Cn, Cn)
     return dx
 
 
@@ -1620,7 +1599,7 @@ def maxpool2x2_bwd(x, dy):
     _chk_f16(dy, "maxpool2x2_bwd.dy")
     B, H2, W2, Cn = x.shape
     dx = torch.empty_like(x)
-    _lib.check(_lib.lib().af_maxpool2x2_bwd(_p(x), _p(dy), _p(dx), B, H2 // 2, W2 // 2, Cn, _stream()), "af_maxpool2x2_bwd")
+    _launch("af_maxpool2x2_bwd", _p(x), _p(dy), _p(dx), B, H2 // 2, W2 // 2, Cn)
     return dx
 
 
@@ -1629,8 +1608,7 @@ def se_gate_grad(x, se_logits, residual, slope, dy):
     _chk_f16(dy, "se_gate_grad.dy")
     B, H, W, Cn = x.shape
     dgl = torch.empty((B, Cn), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_se_gate_grad(_p(x), _p(se_logits), _p(residual), _p(slope), _p(dy), _p(dgl), B, H * W, Cn, _stream()),
-               "af_se_gate_grad")
+    _launch("af_se_gate_grad", _p(x), _p(se_logits), _p(residual), _p(slope), _p(dy), _p(dgl), B, H * W, Cn)
     return dgl
 
 
@@ -1639,8 +1617,7 @@ def se_residual_prelu_bwd(x, se_logits, residual, slope, dy, dpool=None):
     _chk_f16(dy, "se_residual_prelu_bwd.dy")
     B, H, W, Cn = x.shape
     dx, dres = torch.empty_like(x), torch.empty_like(x)
-    _lib.check(_lib.lib().af_se_residual_prelu_bwd(_p(x), _p(se_logits), _p(residual), _p(slope), _p(dy), _p(dpool), _p(dx), _p(dres), B,
-                                                   H * W, Cn, _stream()), "af_se_residual_prelu_bwd")
+    _launch("af_se_residual_prelu_bwd", _p(x), _p(se_logits), _p(residual), _p(slope), _p(dy), _p(dpool), _p(dx), _p(dres), B, H * W, Cn)
     return dx, dres
 
 
@@ -1684,7 +1661,7 @@ def face_alpha_mask(ellipses, photo_hw, feather):
         raise RuntimeError(f"face_alpha_mask: feather must be finite and >= 0, got {feather}")
     alpha = torch.empty((H, W), dtype=torch.float32, device=ellipses.device)
     nf = ellipses.shape[0]
-    _lib.check(_lib.lib().af_face_alpha_mask(_p(ellipses) if nf else None, _p(alpha), nf, H, W, feather, _stream()), "af_face_alpha_mask")
+    _launch("af_face_alpha_mask", _p(ellipses) if nf else None, _p(alpha), nf, H, W, feather)
     return alpha
 
 
@@ -1701,8 +1678,7 @@ def crop_resize_u8(photo_u8, alpha, rect, work_hw, thr=1.0 / 255.0):
         raise RuntimeError(f"crop_resize_u8: the working size must be positive multiples of 8 below 2^31 bytes, got {Ws} x {Hs}")
     image = torch.empty((1, Hs, Ws, 3), dtype=torch.uint8, device=photo_u8.device)
     mask_lat = torch.empty((1, 1, Hs // 8, Ws // 8), dtype=torch.float32, device=photo_u8.device)
-    _lib.check(_lib.lib().af_crop_resize_u8(_p(photo_u8), _p(alpha), _p(image), _p(mask_lat), H, W, x0, y0, cw, ch, Hs, Ws, float(thr),
-                                            _stream()), "af_crop_resize_u8")
+    _launch("af_crop_resize_u8", _p(photo_u8), _p(alpha), _p(image), _p(mask_lat), H, W, x0, y0, cw, ch, Hs, Ws, float(thr))
     return image, mask_lat
 
 
@@ -1723,8 +1699,7 @@ def paste_back_u8(decoded, photo_u8, alpha, rect):
         raise RuntimeError(f"paste_back_u8: {B} photos of {W} x {H} (or decoded {tuple(decoded.shape)}) need 2^31 bytes / elements or more; "
                            "split the batch")
     out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=photo_u8.device)
-    _lib.check(_lib.lib().af_paste_back_u8(_p(decoded), _p(photo_u8), _p(alpha), _p(out), B, Hs, Ws, H, W, x0, y0, cw, ch, _stream()),
-               "af_paste_back_u8")
+    _launch("af_paste_back_u8", _p(decoded), _p(photo_u8), _p(alpha), _p(out), B, Hs, Ws, H, W, x0, y0, cw, ch)
     return out
 
 
@@ -1764,8 +1739,7 @@ def dense_conv3x3(x, cin, wt, bias, out, out_ch, cout, r1=None, r1_ch=0, alpha=1
     po, ldo = _slice_ptr(out, out_ch, cout, grid, "dense_conv3x3.out")
     p1, ld1 = _slice_ptr(r1, r1_ch, cout, grid, "dense_conv3x3.r1") if r1 is not None else (None, 0)
     p2, ld2 = _slice_ptr(r2, r2_ch, cout, grid, "dense_conv3x3.r2") if r2 is not None else (None, 0)
-    _lib.check(_lib.lib().af_dense_conv3x3(_p(x), ldx, cin, _p(wt), _p(bias), po, ldo, cout, p1, ld1, alpha, p2, ld2, beta, slope,
-                                           int(upsample), 0, B, H, W, _stream()), "af_dense_conv3x3")
+    _launch("af_dense_conv3x3", _p(x), ldx, cin, _p(wt), _p(bias), po, ldo, cout, p1, ld1, alpha, p2, ld2, beta, slope, int(upsample), 0, B, H, W)
     return out
 
 
@@ -1775,8 +1749,7 @@ def dense_conv3x3_u8(x, cin, wt, bias, cout, slope=0.0, upsample=False):
     B, H, W, ldx = x.shape
     s = 2 if upsample else 1
     out = torch.empty((B, s * H, s * W, cout), dtype=torch.uint8, device=x.device)
-    _lib.check(_lib.lib().af_dense_conv3x3(_p(x), ldx, cin, _p(wt), _p(bias), _p(out), 0, cout, None, 0, 1.0, None, 0, 1.0, slope,
-                                           int(upsample), 1, B, H, W, _stream()), "af_dense_conv3x3")
+    _launch("af_dense_conv3x3", _p(x), ldx, cin, _p(wt), _p(bias), _p(out), 0, cout, None, 0, 1.0, None, 0, 1.0, slope, int(upsample), 1, B, H, W)
     return out
 
 
@@ -1787,7 +1760,7 @@ def u8_unshuffle_f16(img_u8: torch.Tensor, r: int, cpad: int) -> torch.Tensor:
                            f"{tuple(img_u8.shape)} on {img_u8.device}")
     B, H, W, _ = img_u8.shape
     out = torch.empty((B, H // max(r, 1), W // max(r, 1), cpad), dtype=F16, device=img_u8.device)
-    _lib.check(_lib.lib().af_u8_unshuffle_f16(_p(img_u8), _p(out), B, H, W, r, cpad, _stream()), "af_u8_unshuffle_f16")
+    _launch("af_u8_unshuffle_f16", _p(img_u8), _p(out), B, H, W, r, cpad)
     return out
 
 
@@ -1819,21 +1792,20 @@ def hint_conv3x3(x: torch.Tensor, wt: torch.Tensor, bias: Optional[torch.Tensor]
         raise RuntimeError(f"hint_conv3x3: bias must be a contiguous fp32 device tensor [{cout}], got {bias.dtype} {tuple(bias.shape)}")
     s = int(stride)
     out = torch.empty((B, (H - 1) // max(s, 1) + 1, (W - 1) // max(s, 1) + 1, cout), dtype=F16, device=x.device)
-    _lib.check(_lib.lib().af_hint_conv3x3(_p(x), mode, cin, _p(wt), _p(bias), _p(out), cout, s, int(bool(act)), B, H, W, _stream()),
-               "af_hint_conv3x3")
+    _launch("af_hint_conv3x3", _p(x), mode, cin, _p(wt), _p(bias), _p(out), cout, s, int(bool(act)), B, H, W)
     return out
 
 
 # ----------------------------------------------------------------------------- profiling hook
 def prof_enable(on: bool):
-    _lib.check(_lib.lib().af_prof_enable(int(on)), "af_prof_enable")
+    _checked("af_prof_enable", int(on))
 
 
 def prof_reset():
-    _lib.check(_lib.lib().af_prof_reset(), "af_prof_reset")
+    _checked("af_prof_reset")
 
 
 def prof_read(family: int):
     n, ms = C.c_int(0), C.c_double(0.0)
-    _lib.check(_lib.lib().af_prof_read(family, C.byref(n), C.byref(ms)), "af_prof_read")
+    _checked("af_prof_read", family, C.byref(n), C.byref(ms))
     return n.value, ms.value

@@ -1,5 +1,6 @@
 """CPU-side checks: the C-ABI library builds/loads and exports exactly what include/adaface_hip.h declares,
-the ctypes struct mirrors the C struct, and the host-side weight re-layout is what the kernels expect.
+the binding _lib.py parses out of that header (prototypes, types, struct, constants) is what gcc reads there and refuses what it cannot
+read, and the host-side weight re-layout is what the kernels expect.
 No compute calls are made (no GPU here)."""
 import ctypes
 import os
@@ -34,6 +35,8 @@ def test_library_exports_every_declared_symbol(lib):
     exported = sorted(set(re.findall(r" T (af_[a-z0-9_]+)", out)))
     assert exported == declared, (set(declared) ^ set(exported))
     assert sorted(lib.EXPORTS) == declared
+    # nothing skipped: what the strict parser read is what the loose regex above finds
+    assert sorted(lib.FUNCTIONS) == declared and sorted(lib.parse_header(open(lib.HEADER).read())[0]) == declared
     L = lib.lib()
     for name in declared:
         getattr(L, name)
@@ -83,6 +86,66 @@ def test_gemm_desc_matches_c_struct(lib, tmp_path):
     vals = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
     assert vals[0] == ctypes.sizeof(lib.GemmDesc)
     assert vals[1:] == [getattr(lib.GemmDesc, f).offset for f in fields]
+
+
+def _gcc(tmp_path, name, body, *flags):
+    c = tmp_path / name
+    c.write_text('#include <stdio.h>\n#include "adaface_hip.h"\n' + body)
+    return subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), *flags, str(c)], capture_output=True, text=True)
+
+
+def test_parsed_prototypes_are_the_compilers(lib, tmp_path):
+    """Every prototype as the binding parsed it, written back as a function-pointer type, is the type gcc gives the declared function --
+    and one altered parameter is not (the check can fail)."""
+    def program(functions):
+        return "".join(f"static {ret} (*const p{i})({', '.join(params) or 'void'}) = {name};\n"
+                       for i, (name, (ret, params)) in enumerate(functions.items()))
+    flags = ("-fsyntax-only", "-Werror=incompatible-pointer-types")
+    assert len(lib.FUNCTIONS) >= 103
+    r = _gcc(tmp_path, "protos.c", program(lib.FUNCTIONS), *flags)
+    assert r.returncode == 0, r.stderr
+    ret, params = lib.FUNCTIONS["af_silu_f16"]
+    assert params[2] == "int64_t"
+    altered = dict(lib.FUNCTIONS, af_silu_f16=(ret, params[:2] + ["int"] + params[3:]))
+    r = _gcc(tmp_path, "altered.c", program(altered), *flags)
+    assert r.returncode != 0 and "af_silu_f16" in r.stderr and "incompatible-pointer-types" in r.stderr, r.stderr
+
+
+def test_type_table_and_constants_are_the_compilers(lib, tmp_path):
+    """sizeof of every type spelling the parser accepts == ctypes.sizeof of the type it maps to; every AF_* constant has gcc's value."""
+    spellings, names = sorted(lib.CTYPES), sorted(k for k in vars(lib) if k.startswith("AF_") and isinstance(getattr(lib, k), int))
+    assert {"AF_OK", "AF_E_BADARG", "AF_ACT_GEGLU", "AF_OUT_F32", "AF_FAM_XATTN", "AF_SPLITK_MAX_TILES", "AF_SPLITK_COUNTER_BYTES"} <= set(names)
+    body = "int main(void){\n" + "".join(f'printf("%zu\\n", sizeof({s}));\n' for s in spellings)
+    body += "".join(f'printf("%lld\\n", (long long)({n}));\n' for n in names) + "return 0;}\n"
+    exe = tmp_path / "sizes"
+    r = _gcc(tmp_path, "sizes.c", body, "-o", str(exe))
+    assert r.returncode == 0, r.stderr
+    vals = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert vals[:len(spellings)] == [ctypes.sizeof(lib.CTYPES[s]) for s in spellings]
+    assert vals[len(spellings):] == [getattr(lib, n) for n in names]
+    assert lib.AF_SPLITK_COUNTER_BYTES == 4 * lib.AF_SPLITK_MAX_TILES
+
+
+@pytest.mark.parametrize("decl, named", [
+    ("int af_new_thing(const void* x, size_t n, void* stream);", "af_new_thing"),              # a type outside the table
+    ("int af_new_thing(const void* x, int n[4], void* stream);", "af_new_thing"),              # an array parameter
+    ("int af_new_thing(const void* x, void (*done)(int), void* stream);", "af_new_thing"),     # a function pointer
+    ("int af_new_thing(const void* x, int, void* stream);", "af_new_thing"),                   # a parameter without a name
+    ("int af_new_thing();", "af_new_thing"),                                                    # no prototype
+    ("unsigned af_new_thing(void);", "af_new_thing"),                                           # a return type outside the table
+    ("typedef struct af_gemm_desc { const void* a1; uint16_t flags; } af_gemm_desc;", "uint16_t flags"),
+    ("typedef struct af_gemm_desc { const void* a1; int32_t dims[3]; } af_gemm_desc;", "int32_t dims[3]"),
+    ("#define AF_NEW_LIMIT 1.5", "AF_NEW_LIMIT"),
+    ("#define AF_NEW_LIMIT", "AF_NEW_LIMIT"),
+])
+def test_parser_refuses_what_it_cannot_read(lib, decl, named):
+    """A declaration outside the header's subset of C stops the import and is named; nothing is skipped, no type is guessed."""
+    good = "#define AF_OK 0\n/* a comment with af_not_a_function( in it */\nint af_version(void);\nint af_silu_f16(const void* x, void* y, int64_t n, void* stream);\n"
+    functions, fields, constants = lib.parse_header(good)
+    assert functions == {"af_version": ("int", []), "af_silu_f16": ("int", ["const void*", "void*", "int64_t", "void*"])}
+    assert fields == [] and constants == {"AF_OK": 0}
+    with pytest.raises(RuntimeError, match=re.escape(named)):
+        lib.parse_header(good + decl + "\n")
 
 
 def test_weight_packing_layouts():
