@@ -24,6 +24,9 @@
 namespace {
 
 constexpr int TST = 36;  // transposed-tile LDS row stride in halves (72 B, conflict-free ds_read_b64)
+// With a key bias (make_keybias: 0 / -FLT_MAX) the forward stores lse = -FLT_MAX for a query whose keys are all masked: -FLT_MAX + log2(L)
+// rounds back to -FLT_MAX.  An lse below this marks such a row.
+constexpr float kMaskedBelow = -0.5f * FLT_MAX;
 
 struct BwdArgs {
   const half_t* q;    // [B, Nq, ldq]
@@ -160,7 +163,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(BwdArgs a) {
     }
   }
   const int qsafe = query < a.Nq ? query : 0;
-  const float lse = a.lse2[((size_t)b * a.heads + h) * a.ld_lse + qsafe];
+  // A query whose keys are ALL masked has the uniform P = 1/L, and its dz is zero: every key's score is the masked_fill constant, which
+  // cuts the gradient.  (Rows with a visible key need nothing: p underflows to 0 at their masked keys.)  exp2(t - lse) would be
+  // exp2(-FLT_MAX + FLT_MAX) = 1 there; lse = +inf makes it p = 0, so dz = 0 and the row adds nothing to dQ.
+  const float lse_in = a.lse2[((size_t)b * a.heads + h) * a.ld_lse + qsafe];
+  const float lse = a.kbias && lse_in < kMaskedBelow ? INFINITY : lse_in;
   const float delta = a.delta[((size_t)b * a.heads + h) * a.nqpad + qsafe];
 
   const half_t* kb = a.k + (size_t)b * a.L * a.ldk;
@@ -412,6 +419,31 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(BwdArgs a) {
     };
     if (a.causal_m > 0 || q0 + 32 > a.Nq) softmax_block(std::true_type{});
     else softmax_block(std::false_type{});
+    if (a.kbias) {
+      // queries whose keys are all masked (see the dQ kernel): the block above recomputed p = exp2(0) = 1 for them.  P is 1/L there, and it
+      // reaches dV only: dz is zero.  Kept out of the block above, which is VALU-bound; a stage without such a query skips the rewrite.
+      float lo = 0.f;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const floatx4 lse = *reinterpret_cast<const floatx4*>(lseb + q0 + 8 * g + 4 * hh);
+        lo = fminf(lo, fminf(fminf(lse[0], lse[1]), fminf(lse[2], lse[3])));
+      }
+      if (__builtin_amdgcn_ballot_w64(lo < kMaskedBelow) != 0) {
+        const half_t pu = (half_t)(key_ok ? 1.0f / (float)a.L : 0.f);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int qq = q0 + 8 * g + 4 * hh;
+          const floatx4 lse = *reinterpret_cast<const floatx4*>(lseb + qq);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int i = 4 * g + e;
+            const bool dead = lse[e] < kMaskedBelow && qq + e < a.Nq;   // padding rows of lse may hold anything
+            pf[i >> 3][i & 7] = dead ? pu : pf[i >> 3][i & 7];
+            zf[i >> 3][i & 7] = dead ? (half_t)0.f : zf[i >> 3][i & 7];
+          }
+        }
+      }
+    }
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll

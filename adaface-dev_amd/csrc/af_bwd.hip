@@ -348,8 +348,13 @@ __global__ __launch_bounds__(256) void axpy_f16_kernel(const half_t* __restrict_
   if (i >= n8) return;
   const half8_t x = *reinterpret_cast<const half8_t*>(a + i * 8), y = *reinterpret_cast<const half8_t*>(b + i * 8);
   half8_t o;
+  // product and sum rounded separately, bit for bit torch's a + alpha * b in fp32: contracted into one fma the result differs in the
+  // last fp16 bit for about one element in a thousand when alpha is not a power of two
 #pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)x[e] + alpha * (float)y[e]);
+  for (int e = 0; e < 8; ++e) {
+#pragma clang fp contract(off)
+    o[e] = (half_t)((float)x[e] + alpha * (float)y[e]);
+  }
   *reinterpret_cast<half8_t*>(out + i * 8) = o;
 }
 
@@ -611,7 +616,10 @@ __global__ __launch_bounds__(256) void quickgelu_bwd_kernel(const half_t* __rest
 
 __global__ __launch_bounds__(256) void clamp_f32_kernel(float* __restrict__ a, float lo, float hi, long n) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) a[i] = fminf(fmaxf(a[i], lo), hi);       // NaN stays NaN (the overflow check runs before the clip)
+  if (i < n) {
+    const float x = a[i];
+    a[i] = x != x ? x : fminf(fmaxf(x, lo), hi);      // NaN stays NaN as in torch.clamp (fmaxf(NaN, lo) alone returns lo)
+  }
 }
 
 __global__ __launch_bounds__(256) void scale_f32_kernel(float* __restrict__ a, float s, long n) {
