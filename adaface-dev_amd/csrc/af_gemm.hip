@@ -44,6 +44,8 @@ struct GemmDev {
   int* counters;             // in-kernel split-K reduction: per-tile arrival counters (zero between launches); nullptr = reduce pass
   int out_f32;               // AF_OUT_F32: the reduce pass stores fp32
   int wpf, wpf_coop;         // weight-tile L2 prefetch at kernel start (af_common.h): instructions per wave (0 = off), sharing workgroups
+  int up2_cout;              // reduce pass of the phase form under split-K (upsample = 3 on a whole-line tile): Cout; the slabs are [M = B H W low-res
+                             // pixels][N = 4 Cout phase-major] and H / W the LOW-res image; 0 = rows and columns go where they are
 };
 
 constexpr int BK = 64;
@@ -537,6 +539,18 @@ __global__ __launch_bounds__(256) void af_splitk_reduce_kernel(GemmDev p) {
   const int n0 = (int)(i4 - (long)m * n4) * 4;
   floatx4 v = {0.f, 0.f, 0.f, 0.f};
   for (int sp = 0; sp < p.splits; ++sp) v += *reinterpret_cast<const floatx4*>(p.ws + ((size_t)sp * p.M + m) * p.N + n0);
+  if (p.up2_cout > 0) {
+    // the phase form of the nearest-x2 convolution: slab row m = low-res pixel (b, y, x), column n0 = phase * Cout + channel, phase = 2 py + px;
+    // the sum goes to hi-res pixel (b, 2 y + py, 2 x + px), the same destination as the halo-resident kernel's staged epilogue (gemm3_epilogue, UP2).
+    // Four consecutive columns never straddle a phase (4 | Cout); the bias only -- the host refuses everything else
+    const int ph = n0 / p.up2_cout, ch = n0 - ph * p.up2_cout;
+    const int hw = p.H * p.W, b = m / hw, rem = m - b * hw, y = rem / p.W, x = rem - y * p.W;
+    const size_t row = ((size_t)b * 2 * p.H + 2 * y + (ph >> 1)) * 2 * p.W + 2 * x + (ph & 1);
+    if (p.bias) v += *reinterpret_cast<const floatx4*>(p.bias + ch);
+    const half4_t h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+    *reinterpret_cast<half4_t*>(p.out + row * p.ld_out + ch) = h;
+    return;
+  }
   if (p.bias) v += *reinterpret_cast<const floatx4*>(p.bias + n0);
   if (p.rowbias) {
     const half4_t rv = *reinterpret_cast<const half4_t*>(p.rowbias + (size_t)(m / p.rows_per_batch) * p.ld_rowbias + n0);
@@ -636,8 +650,36 @@ extern "C" int af_gemm(const af_gemm_desc* d, void* stream) {
   if (d->upsample == 3) {
     // nearest x2 + 3x3 as four 2x2 phase convolutions (weights from the phase pack, K = 4 c1): the halo-resident kernel's phase form or nothing -- no
     // other kernel reads that pack
-    AF_SUPPORTED(d->tile == 14 && af_gemm_halo_variant(d) == 4, "af_gemm: upsample = 3 (phase form) runs on tile 14 inside af_gemm_halo_variant's scope only");
+    const int hv = af_gemm_halo_variant(d);
+    AF_SUPPORTED((d->tile == 14 && hv == 4) || hv == 5, "af_gemm: upsample = 3 (phase form) runs inside af_gemm_halo_variant's scope only: tile 14, or a whole-line "
+                                                        "tile under split-K at the 8 x 8 level");
     AF_REQUIRE(d->zeros != nullptr, "af_gemm: zeros must be non-null");
+    if (hv == 5) {
+      // the 8 x 8 level: the whole-line tap-by-tap kernel walks the LOW-res image with the phase's four taps (af_gemm3.hip) and leaves fp32 slabs
+      // [splits][B H W][4 Cout]; the reduce pass sums them straight into the hi-res fp16 tensor
+      const int eff = af_gemm3_effective_splits(d, d->splits, d->tile - 3);
+      AF_REQUIRE(eff >= 2 && d->workspace != nullptr && d->workspace_bytes >= (int64_t)eff * d->M * d->N * 4,
+                 "af_gemm: the phase form on a whole-line tile needs split-K and workspace >= splits*M*N*4 bytes");
+      const int ldo = d->ld_out ? d->ld_out : d->N;
+      AF_REQUIRE(ldo >= d->N && ldo % 4 == 0 && ((uintptr_t)d->out & 7) == 0 && ((uintptr_t)d->bias & 15) == 0, "af_gemm: upsample = 3 needs an 8-byte aligned output with ld_out % 4 == 0");
+      AfLaunchScope scope(AF_FAM_GEMM, stream);
+      AF_SUPPORTED(af_gemm3_try_launch(d, d->splits, d->tile - 3, (hipStream_t)stream) == 2, "af_gemm: upsample = 3 is outside the chosen whole-line tile's scope");
+      GemmDev r{};
+      r.ws = (float*)d->workspace;
+      r.bias = (const float*)d->bias;
+      r.out = (half_t*)d->out;
+      r.M = d->B * d->H * d->W;
+      r.N = 4 * d->N;
+      r.H = d->H;
+      r.W = d->W;
+      r.up2_cout = d->N;
+      r.ld_out = ldo;
+      r.splits = eff;
+      r.rows_per_batch = r.M;
+      const long n = (long)r.M * (r.N >> 2);
+      hipLaunchKernelGGL(af_splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, r);
+      return af_check_launch("af_gemm(phase form, split-K)");
+    }
     AfLaunchScope scope(AF_FAM_GEMM, stream);
     AF_SUPPORTED(af_gemm3_try_launch(d, 1, 11, (hipStream_t)stream) == 0, "af_gemm: upsample = 3 needs a 16-byte aligned output with ld_out % 8 == 0");
     return af_check_launch("af_gemm(tile 14, phase form)");
@@ -686,6 +728,7 @@ extern "C" int af_gemm(const af_gemm_desc* d, void* stream) {
   p.act_silu = d->act == AF_ACT_SILU ? 1 : (d->act == AF_ACT_QUICKGELU ? 3 : 0);
   p.split_col = d->split_col;
   p.ld_out2 = d->ld_out2;
+  p.up2_cout = 0;
   p.tiles_n = 0;
   p.tap_shift = d->taps == 9 ? d->tap_shift : 0;
   p.splits = d->splits > 1 ? d->splits : 1;

@@ -57,7 +57,8 @@ struct Gemm3Dev {
   int patch_tx;         // halo-resident kernel, PATCH form (images wider than 64 pixels): 16 x 16-pixel tiles, patch_tx of them per image row, patch_tpi per image
   int patch_tpi;
   int up2_cout;         // halo-resident kernel, phase form of the nearest-x2 convolution (af_gemm_desc.upsample = 3): Cout.  N = 4 Cout phase-major rows and
-                        // H / W / Ho / Wo / HoWo describe the LOW-res image the kernel walks on; M stays the number of output rows
+                        // H / W / Ho / Wo / HoWo describe the LOW-res image the kernel walks on; M stays the number of output rows.  The whole-line kernel
+                        // (the 8 x 8 level under split-K) takes the same fields with M = the low-res rows
 };
 
 constexpr int BK3 = 32;
@@ -863,6 +864,17 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSLOT == 2) ? 2 
     }
   }
 
+  // The phase form of the nearest-x2 convolution on this kernel (the 8 x 8 level, under split-K; host: conv3w_up2_ok): a stride-1 walk over the
+  // LOW-res image with N = 4 Cout phase-major weight rows and K = 4 Cin.  An N tile lies in ONE phase (BN | Cout), phase = 2 py + px, and reads
+  // the taps {py, py + 1} x {px, px + 1} of the nine: up2_tap0 is the first of them.  Scalar; 0 and unused everywhere else.
+  int up2_tap0 = 0;
+  if constexpr (TAPS == 9) {
+    if (p.up2_cout > 0) {
+      const int ph = (tile_n * BN) / p.up2_cout;
+      up2_tap0 = (ph >> 1) * 3 + (ph & 1);
+    }
+  }
+
   auto issue_stage = [&](int kt, int sl) {
     char* As = af_smem + sl * STAGE;
     char* Ws = As + BM * 128;
@@ -904,8 +916,10 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSLOT == 2) ? 2 
         for (int j = 0; j < APW; ++j) glds16_sbase(sb, a_off2[j], As + (wave * APW + j) * 1024);
       }
     } else if constexpr (TAPS == 9) {
-      const int tp = k0 / Cin;                       // workgroup-uniform (64 | c1, c2)
-      const int c0 = k0 - tp * Cin;
+      const int kq = k0 / Cin;                       // workgroup-uniform (64 | c1, c2)
+      const int c0 = k0 - kq * Cin;
+      // the phase form (p.up2_cout > 0): K block kq = 2 a + b of this N tile's phase (py, px) is tap (py + a, px + b) of the low-res image
+      const int tp = p.up2_cout > 0 ? up2_tap0 + (kq >> 1) * 3 + (kq & 1) : kq;
       const bool first = c0 < p.c1;
       const int cs = first ? p.c1 : p.c2;
       const int ty = tp / 3, tx = tp - ty * 3;
@@ -1809,11 +1823,12 @@ __global__ __launch_bounds__(512) void af_conv3hd_kernel(const Gemm3Dev p) {
 // before it gets here).
 // 0 = outside; 1 = the 256 x 160 tile on whole image rows (the U-Net's levels); 2 = the 256 x 128 tile on whole image rows; 3 = the 256 x 128 tile on
 // 16 x 16-pixel patches (images wider than 64 pixels: the VAE decoder's 128 / 256 / 512 levels); 4 = the phase form of the nearest-x2 convolution
-// (upsample = 3): the 256 x 160 tile on whole rows of the LOW-res image, four stages per chunk
+// (upsample = 3): the 256 x 160 tile on whole rows of the LOW-res image, four stages per chunk; 5 = the phase form at the 8 x 8 level, which runs on the
+// whole-line tile d->tile under split-K, not on this kernel (conv3w_up2_ok)
 //
 // The phase form's scope: one source, 64-multiples of input channels, Cout % 160 == 0 (an N tile lies in one phase), W in {16, 32} and whole 256-pixel tiles
 // per image (halo 18 x 18 = 324 or 10 x 34 = 340 pixels: at most 43 pieces, the six per wave its loop issues), no split-K, nothing in the epilogue but the bias
-// (and an activation).  Not the 8 x 8 level (it needs split-K with a phase-mapped reduce), not the patch form, not 128-multiples of channels.
+// (and an activation).  Not the 8 x 8 level (split-K with a phase-mapped reduce: variant 5 below), not the patch form, not 128-multiples of channels.
 static bool conv3h_up2_ok(const af_gemm_desc* d) {
   if (d->taps != 9 || d->tap_shift || (d->stride ? d->stride : 1) != 1 || d->c1 <= 0 || d->c1 % 64 != 0 || d->c2 || d->c3 || d->c4) return false;
   if (d->N <= 0 || d->N % CH_BN != 0 || d->K != 4 * d->c1 || d->kpad % 64 != 0 || d->kpad < d->K) return false;
@@ -1826,8 +1841,25 @@ static bool conv3h_up2_ok(const af_gemm_desc* d) {
   return true;
 }
 
+// The phase form at the 8 x 8 level (variant 5): not on the halo-resident kernel -- 64-pixel images leave it a quarter of a tile and K = 4 Cin wants
+// split-K -- but on the whole-line tap-by-tap kernel, which walks the low-res image with the four taps of its N tile's phase (af_gemm3w_kernel, up2_tap0)
+// and leaves fp32 slabs that af_splitk_reduce_kernel sums straight into the hi-res tensor.  Scope: d->tile one of the whole-line tiles 7 / 8 / 11 / 12 / 13
+// whose width divides Cout (an N tile lies in one phase), at least two effective K slices, no K padding, nothing in the epilogue but the bias.
+static bool conv3w_up2_ok(const af_gemm_desc* d) {
+  if (d->taps != 9 || d->tap_shift || (d->stride ? d->stride : 1) != 1 || d->c1 <= 0 || d->c1 % 64 != 0 || d->c2 || d->c3 || d->c4) return false;
+  const int bn = d->tile == 7 ? 320 : ((d->tile == 11 || d->tile == 13) ? 160 : ((d->tile == 8 || d->tile == 12) ? 128 : 0));
+  if (bn == 0 || d->N <= 0 || d->N % bn != 0 || d->K != 4 * d->c1 || d->kpad != d->K) return false;
+  if (d->W != 8 || d->H != 8 || d->B <= 0 || d->Ho != 2 * d->H || d->Wo != 2 * d->W || (long)d->M != (long)d->B * d->Ho * d->Wo) return false;
+  if (d->splits < 2 || d->splits > 16 || d->splits > d->kpad / 64) return false;       // (then no slice is empty and at least two are left)
+  if (d->act != AF_ACT_NONE || d->out_mode != AF_OUT_NORMAL || d->ln_colsum != nullptr) return false;
+  if (d->rowbias != nullptr || d->residual != nullptr || d->gn_partials != nullptr) return false;
+  if ((long)d->M * d->c1 * 2 >= (1L << 32)) return false;                                     // the loaders' 32-bit byte offsets
+  if ((long)((4L * d->N + 127) / 128 * 128) * d->kpad * 2 >= (1L << 32)) return false;
+  return true;
+}
+
 static int conv3h_variant(const af_gemm_desc* d) {
-  if (d->upsample == 3) return conv3h_up2_ok(d) ? 4 : 0;
+  if (d->upsample == 3) return conv3h_up2_ok(d) ? 4 : (conv3w_up2_ok(d) ? 5 : 0);
   if (d->taps != 9 || (d->upsample != 0 && d->upsample != 1) || d->tap_shift || d->c1 % 64 != 0 || d->c2 % 64 != 0) return 0;
   const bool n160 = d->N % CH_BN == 0;
   if (!n160 && d->N % 128 != 0) return 0;
@@ -2203,7 +2235,8 @@ int af_gemm3_try_launch(const af_gemm_desc* d, int splits, int wide, hipStream_t
   const int halo_variant = wide == 11 ? conv3h_variant(d) : 0;
   if (wide == 11 && halo_variant == 0) return 1;                // halo-resident 3x3 kernel (tile 14)
   if (halo_r5 && (d->c3 > 0 || halo_variant != 1)) return 1;    // (the K tail and the 256 x 128 forms exist in the round-6 loop only)
-  if (d->upsample == 3 && halo_variant != 4) return 1;          // the phase form: tile 14 inside conv3h_up2_ok, nothing else
+  const bool up2w = d->upsample == 3 && wide != 11 && d->tile == wide + 3 && splits == d->splits && conv3h_variant(d) == 5;   // the phase form on a whole-line tile (the 8 x 8 level)
+  if (d->upsample == 3 && halo_variant != 4 && !up2w) return 1;  // the phase form: tile 14 inside conv3h_up2_ok, a whole-line tile inside conv3w_up2_ok, nothing else
   if (d->upsample && d->upsample != 3 && !((wide == 4 || wide == 5 || (wide >= 8 && wide <= 12)) && d->upsample == 1 && d->taps == 9)) return 1;   // nearest x2: whole-line kernel only
   if (d->c1 % BK3 != 0 || d->c2 % BK3 != 0 || d->zeros == nullptr) return 1;
   if (d->c3 > 0 && (wide < 4 || (wide > 10 && wide != 12 && wide != 11) || d->taps != 9 || d->upsample || (d->stride != 0 && d->stride != 1))) return 1;   // K tail: whole-line tap-by-tap tiles + the halo-resident kernel
@@ -2285,6 +2318,17 @@ int af_gemm3_try_launch(const af_gemm_desc* d, int splits, int wide, hipStream_t
   p.wpf_coop = 1;                                              // know tiles_m; the ring kernel has none
   static const int ablate = getenv("AF_GEMM3_ABLATE") ? atoi(getenv("AF_GEMM3_ABLATE")) : 0;
   p.ablate = ablate & (128 | 256);                             // the whole-line kernel's two main-loop switches; nothing else reads the mask
+  if (up2w) {                                                  // the kernel sees a stride-1 convolution of the low-res image: B H W rows, 4 Cout phase-major columns,
+    p.up2_cout = d->N;                                         // four taps per column tile; it only ever leaves slabs (splits >= 2, reduced by the caller's pass)
+    p.M = d->B * d->H * d->W;
+    p.N = 4 * d->N;
+    p.npad = (p.N + 127) / 128 * 128;
+    p.Ho = d->H;
+    p.Wo = d->W;
+    p.HoWo = d->H * d->W;
+    p.upsample = 0;
+    p.counters = nullptr;
+  }
   {
     // the whole-line kernel's loaders hold 32-bit byte offsets into the row-addressed operands (round 6): anything larger goes to the register-staged kernel
     const long ldmax = std::max(std::max((long)(d->lda1 ? d->lda1 : d->c1), (long)(d->lda2 ? d->lda2 : d->c2)), std::max((long)(d->lda3 ? d->lda3 : d->c3), (long)(d->lda4 ? d->lda4 : d->c4)));

@@ -35,7 +35,9 @@ FUSE_GN_PROJ = _os.environ.get("AF_FUSE_GN_PROJ", "1") != "0"      # SpatialTran
 CHAIN_XATTN = _os.environ.get("AF_CHAIN_XATTN", "1") != "0"    # round 6: the self-attention's to_out + residual as phase 0 of the one-launch C = 320 cross-attention block (af_xattn_chain)
 XATTN_FUSE_MIN_TOKENS = int(_os.environ.get("AF_XATTN_FUSE_MIN_TOKENS", "8192"))   # U-Net batch x tokens from which the one-launch block is used
 CHAIN_PROJ_OUT = _os.environ.get("AF_CHAIN_PROJ_OUT", "1") != "0"   # the SpatialTransformer's proj_out + residual as the tail of the one-launch feed-forward at C = 320 (af_ff_chain, round 6)
-FUSE_XATTN640 = _os.environ.get("AF_FUSE_XATTN640", "0") != "0"  # the C = 640 blocks as one launch too (af_xattn640t_kernel, round 6): measured, see DESIGN.md 8.0
+FOLD_PROJ_OUT = _os.environ.get("AF_FOLD_PROJ_OUT", "1") != "0"     # where the feed-forward does not run as af_ff_chain (C = 640 / 1280): proj_out folded into ff.net[2]'s weights at pack
+                                                                    # time, one K-concatenated GEMM over [g ; x2] (ops.pack_ff_proj_out); 0 = the two GEMMs (A/B runs)
+FUSE_XATTN640 =_os.environ.get("AF_FUSE_XATTN640", "0") != "0"  # the C = 640 blocks as one launch too (af_xattn640t_kernel, round 6): measured, see DESIGN.md 8.0
 XATTN640_FUSE_MIN_TOKENS = 4096                                   # 64-token workgroups: 64 of them at least
 FUSE_XATTN = _os.environ.get("AF_FUSE_XATTN", "1") != "0"      # the C = 320 cross-attention block as ONE launch (af_xattn_fused): on par with the
                                                                 # three launches alone, -0.03 ms per denoise step (csrc/af_xattn_fused.hip); 0 = three launches
@@ -128,10 +130,14 @@ class FeedForward(nn.Module):
         return bool(FUSE_FF and ln is not None and C == 320 and M >= 24576)
 
     def hip(self, x2d, residual=None, ln=None, post=None):
-        """post = (proj_out pack, x_in 2-D, rows per image, gn_cpg): the SpatialTransformer's proj_out + residual chained behind (af_ff_chain; the caller checked ff_fusable)."""
+        """post = (proj_out pack, x_in 2-D, rows per image, gn_cpg, fold): the SpatialTransformer's proj_out + residual run here too (the caller asked
+        BasicTransformerBlock.post_done) -- chained behind the one-launch feed-forward where that runs (af_ff_chain), else folded into the second
+        projection: ``fold()`` is the [W_p W2 | W_p] pack and the GEMM reads [g ; residual]."""
         if post is not None:
-            pw_p, x_in, rpb, cpg = post
-            return ops.ff_chain(x2d, self.net[0].packed_ln(ln), self.net[2].packed(), residual, pw_p, x_in, rows_per_batch=rpb, gn_cpg=cpg)
+            pw_p, x_in, rpb, cpg, fold = post
+            if self.ff_fusable(x2d.shape[0], x2d.shape[1], ln):
+                return ops.ff_chain(x2d, self.net[0].packed_ln(ln), self.net[2].packed(), residual, pw_p, x_in, rows_per_batch=rpb, gn_cpg=cpg)
+            return ops.gemm(self.net[0].hip(x2d, ln=ln), fold(), a2=residual, residual=x_in, rows_per_batch=rpb, gn_cpg=cpg)
         if FUSE_FF and ln is not None and x2d.shape[1] == 320 and x2d.shape[0] >= 24576:
             # the 64 x 64 level: LayerNorm, GEGLU projection, output projection and residual as ONE launch (af_ff_fused): the
             # [tokens, 1280] intermediate never leaves the compute unit.  One workgroup per 128 tokens: worth it once they fill the chip
@@ -334,8 +340,8 @@ class BasicTransformerBlock(nn.Module):
 
     def hip(self, x2d, B, N, context=None, keybias=None, post=None):
         """attention.py:242-252 with the three residual adds fused into GEMM epilogues.  post (SpatialTransformer.hip, its LAST block only) = (proj_out pack, x_in 2-D,
-        rows per image, gn_cpg): proj_out + residual run as the tail of the one-launch feed-forward where that runs (af_ff_chain) -- the return value is then the
-        SpatialTransformer's output and ``post_done(...)`` says so."""
+        rows per image, gn_cpg, getter of the folded pack): proj_out + residual run as the tail of the one-launch feed-forward where that runs (af_ff_chain),
+        else folded into the feed-forward's second GEMM (FOLD_PROJ_OUT) -- the return value is then the SpatialTransformer's output and ``post_done(...)`` says so."""
         if FOLD_LAYERNORM and x2d.shape[1] % 64 == 0:
             # the LayerNorms do not run as kernels: each is folded into the projection GEMM that consumes it.  Below ~1,000 rows (the
             # 8 x 8 level) the q | k | v and to_q GEMMs sit on the register-staged 64 x 64 tile, which has no fold, and a 3.8 us LayerNorm
@@ -355,8 +361,13 @@ class BasicTransformerBlock(nn.Module):
         return self.ff.hip(self.norm3.hip(x2), residual=x2)
 
     def post_done(self, M, C, post) -> bool:
-        """Whether ``hip(..., post=post)`` on [M, C] rows runs the caller's proj_out + residual itself (the one-launch feed-forward with its tail, af_ff_chain)."""
-        return bool(post is not None and CHAIN_PROJ_OUT and FOLD_LAYERNORM and C % 64 == 0 and self.ff.ff_fusable(M, C, self.norm3))
+        """Whether ``hip(..., post=post)`` on [M, C] rows runs the caller's proj_out + residual itself: as the tail of the one-launch feed-forward
+        (af_ff_chain, C = 320), or, where the feed-forward is two GEMMs, folded into the second one (FOLD_PROJ_OUT; post[4] is then the pack's getter)."""
+        if post is None or not FOLD_LAYERNORM or C % 64 != 0:
+            return False
+        if self.ff.ff_fusable(M, C, self.norm3):
+            return CHAIN_PROJ_OUT
+        return bool(FOLD_PROJ_OUT and post[4] is not None)
 
     def hip_train(self, x2d, B, N, context=None, keybias=None):
         if FOLD_LAYERNORM and x2d.shape[1] % 64 == 0 and x2d.shape[0] >= 1024:
@@ -419,6 +430,15 @@ class SpatialTransformer(nn.Module):
             kb = torch.where(any_empty, torch.zeros_like(kb), kb)
         return kb
 
+    def _packed_ff_proj_out(self):
+        """ff.net[2] of the last block with proj_out folded behind it (ops.pack_ff_proj_out), cached on the four parameters: any in-place change of one
+        of them (a merged LoRA) repacks."""
+        lin = self.transformer_blocks[-1].ff.net[2]
+        if not hasattr(self, "_fold_cache"):
+            self._fold_cache = _PackCache()
+        return self._fold_cache.get((lin.weight, lin.bias, self.proj_out.weight, self.proj_out.bias),
+                                    lambda: ops.pack_ff_proj_out(lin.weight, lin.bias, self.proj_out.weight, self.proj_out.bias, lin.weight.device))
+
     def hip(self, x, context=None, mask=None):
         """x [B,H,W,C] fp16; context [B,L,Cc] fp16; mask [B,1,h0,w0] (nonzero = keep) or None."""
         B, H, W, Cn = x.shape
@@ -435,12 +455,13 @@ class SpatialTransformer(nn.Module):
         # the partial statistics with it (ops.GnPartials)
         cpg = Cn // 32 if Cn % 32 == 0 else 0
         last = len(self.transformer_blocks) - 1
-        post = (self.proj_out.packed(), x.reshape(B * N, Cn), N, cpg)
+        post = (self.proj_out.packed(), x.reshape(B * N, Cn), N, cpg, self._packed_ff_proj_out)
         chained = False
         for i, block in enumerate(self.transformer_blocks):
             block.attn2.infeat_size = (H, W)
             if i == last and block.post_done(B * N, y.shape[1], post):
-                # round 6: proj_out + residual as the tail of the last block's one-launch feed-forward (C = 320, the 64 x 64 level: af_ff_chain)
+                # proj_out + residual inside the last block's feed-forward: the tail of its one-launch form (C = 320, the 64 x 64 level: af_ff_chain), or
+                # folded into its second projection's weights (C = 640 / 1280: one K = 5 C GEMM over [g ; x2], ops.pack_ff_proj_out)
                 y, chained = block.hip(y, B, N, context, kb, post=post), True
             else:
                 y = block.hip(y, B, N, context, kb)

@@ -109,12 +109,16 @@ class Conv2d(nn.Conv2d):
         """x [B,H,W,C1] (+x2 [B,H,W,C2]) fp16 -> [B,Ho,Wo,Cout] fp16.  gn_groups > 0: the output feeds a GroupNorm of that many groups -- where
         the launch can, it leaves the partial statistics with the tensor (ops.GnPartials) and the GroupNorm skips its statistics pass."""
         if upsample is True and self.kernel_size == (3, 3) and self.stride[0] == 1 and not gn_groups and os.environ.get("AF_UP2_PHASE", "1") != "0":
-            # nearest x2 + 3x3 as four 2x2 phase convolutions where the library's kernel covers the shape (the U-Net's 16 -> 32 and 32 -> 64 levels);
+            # nearest x2 + 3x3 as four 2x2 phase convolutions where the library covers the shape: the U-Net's 16 -> 32 and 32 -> 64 levels on the
+            # halo-resident kernel.  8 -> 16 runs on a whole-line tile under split-K and is OFF by default (AF_UP2_PHASE_8X8=1 switches it on): 62.1 ->
+            # 51.3 us alone, but -0.015 ms per step did not clear the run-to-run spread (DESIGN.md 4.4, profiles/r08_fold_proj_out_up2_8x8.txt).
             # AF_UP2_PHASE=0 (A/B switch, read per call): the nine-tap gather everywhere
             B, H, W, c1 = x.shape
-            d = ops.conv_up2_desc(B, H, W, c1, self.out_channels, c2=0 if x2 is None else x2.shape[-1], rowbias=rowbias, residual=residual)
-            if ops.conv_up2_eligible(d):
-                return ops.conv3x3_up2(x, self.packed_up2(), tile=14, splits=1)
+            tile, splits = ops.conv_up2_config(B, H, W, c1, self.out_channels)
+            d = ops.conv_up2_desc(B, H, W, c1, self.out_channels, c2=0 if x2 is None else x2.shape[-1], rowbias=rowbias, residual=residual,
+                                  tile=tile, splits=splits)
+            if ops.conv_up2_eligible(d) and (tile == 14 or os.environ.get("AF_UP2_PHASE_8X8", "0") != "0"):
+                return ops.conv3x3_up2(x, self.packed_up2(), tile=tile, splits=splits)
         pw = self.packed()
         cpg = self.out_channels // gn_groups if gn_groups and self.out_channels % gn_groups == 0 else 0
         if self.kernel_size == (3, 3):

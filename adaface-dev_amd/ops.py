@@ -179,6 +179,26 @@ def pack_conv3x3_up2(w: torch.Tensor, bias: Optional[torch.Tensor], device) -> P
     return pw
 
 
+def pack_ff_proj_out(w2: torch.Tensor, b2: Optional[torch.Tensor], wp: torch.Tensor, bp: Optional[torch.Tensor], device) -> PackedWeight:
+    """The feed-forward's second projection with the SpatialTransformer's proj_out folded behind it, as ONE K-concatenated GEMM over [g ; x2]:
+        x_in + b_p + W_p (x2 + b2 + W2 g) = x_in + (W_p b2 + b_p) + [W_p W2 | W_p] [g ; x2]
+    -> [C, 4C + C] (w2 [C, 4C], wp [C, C] or [C, C, 1, 1]).  The product and the bias are formed in fp32 from the parameters and rounded to fp16 once,
+    as pack_conv3x3_up2 forms its sums.  A pure function of its four tensors."""
+    w2f = w2.detach().to(device=device, dtype=torch.float32)
+    wpf = wp.detach().to(device=device, dtype=torch.float32).reshape(wp.shape[0], -1)
+    assert wpf.shape[1] == w2f.shape[0], f"pack_ff_proj_out: proj_out takes {wpf.shape[1]} channels, the feed-forward gives {w2f.shape[0]}"
+    b = None
+    if b2 is not None:
+        b = (wpf * b2.detach().to(device=device, dtype=torch.float32)[None, :]).sum(dim=1)
+    if bp is not None:
+        bpf = bp.detach().to(device=device, dtype=torch.float32)
+        b = bpf if b is None else b + bpf
+    # W_p W2 element-wise, a few output rows at a time (at most 2^26 products in flight): no vendor GEMM for a one-off pack, as pack_matrix_ln
+    rows = max(1, (1 << 26) // (wpf.shape[1] * w2f.shape[1]))
+    prod = torch.cat([(wpf[i:i + rows, :, None] * w2f[None, :, :]).sum(dim=1) for i in range(0, wpf.shape[0], rows)], dim=0)
+    return pack_matrix(torch.cat([prod, wpf], dim=1), b, device)
+
+
 def interleave_geglu(w: torch.Tensor, b: torch.Tensor):
     """GEGLU projection [2*inner, C]: rows [value | gate] -> 16-row groups [16 value, 16 gate, ...]
     so value and gate of a channel land in the same lane / register of adjacent MFMA tiles."""
@@ -565,10 +585,24 @@ def conv3x3(x: torch.Tensor, pw: PackedWeight, *, x2: Optional[torch.Tensor] = N
     return out
 
 
-def conv_up2_desc(B: int, H: int, W: int, c1: int, cout: int, *, c2: int = 0, rowbias=None, residual=None, splits: int = 1) -> "GemmDesc":
-    """The descriptor of nearest x2 + 3x3 in its phase form (upsample = 3; K = 4 c1 on the pack_conv3x3_up2 weights), shape and mode fields and the
-    epilogue operands only -- what conv_up2_eligible reads."""
+# The phase form at the 8 x 8 level runs on a whole-line tile under split-K, and which tile and how many slices pay is a per-shape measurement:
+# (output rows, Cout, 4 Cin) -> (tile, splits), the fastest of an isolated sweep (profiles/r08_fold_proj_out_up2_8x8.txt).  Kept apart from
+# tuning/gfx950_gemm.json, whose keys describe launches the tuned-shape sweep can rebuild from the key alone.
+UP2_SPLITK_SHAPES = {(2048, 1280, 5120): (7, 4)}
+
+
+def conv_up2_config(B: int, H: int, W: int, c1: int, cout: int):
+    """(tile, splits) Conv2d.hip asks the phase form of nearest x2 + 3x3 for at this shape: the halo-resident kernel (tile 14, unsplit) -- the 16 x 16
+    and 32 x 32 levels -- or, for the 8 x 8 shapes of UP2_SPLITK_SHAPES, their measured whole-line tile and split count.  An 8 x 8 shape that has not
+    been measured keeps the nine-tap launch (tile 14 is outside the form's scope there: conv_up2_eligible says no)."""
+    return UP2_SPLITK_SHAPES.get((B * 4 * H * W, cout, 4 * c1), (14, 1)) if (H, W) == (8, 8) else (14, 1)
+
+
+def conv_up2_desc(B: int, H: int, W: int, c1: int, cout: int, *, c2: int = 0, rowbias=None, residual=None, tile: int = 14, splits: int = 1) -> "GemmDesc":
+    """The descriptor of nearest x2 + 3x3 in its phase form (upsample = 3; K = 4 c1 on the pack_conv3x3_up2 weights), shape and mode fields, the launch
+    configuration and the epilogue operands only -- what conv_up2_eligible reads."""
     d = GemmDesc()
+    d.tile = tile
     d.rowbias, d.residual = _p(rowbias), _p(residual)
     d.M, d.N, d.K, d.kpad, d.taps = B * 4 * H * W, cout, 4 * c1, round_up(4 * c1, 64), 9
     d.c1, d.c2 = c1, c2
@@ -581,18 +615,24 @@ def conv_up2_desc(B: int, H: int, W: int, c1: int, cout: int, *, c2: int = 0, ro
 
 
 def conv_up2_eligible(d) -> bool:
-    """Whether af_gemm runs the phase-form descriptor ``d`` (conv_up2_desc) -- the library's own launch predicate, as conv_halo_eligible."""
-    return _lib.lib().af_gemm_halo_variant(C.byref(d)) == 4
+    """Whether af_gemm runs the phase-form descriptor ``d`` (conv_up2_desc) -- the library's own launch predicate, as conv_halo_eligible: 4 = the
+    halo-resident kernel's phase form (tile 14, unsplit), 5 = the whole-line tile d.tile under split-K with the phase-mapped reduce (the 8 x 8 level)."""
+    return _lib.lib().af_gemm_halo_variant(C.byref(d)) in (4, 5)
 
 
-def conv3x3_up2(x: torch.Tensor, pw: PackedWeight, *, tile: int = 14, splits: int = 1) -> torch.Tensor:
-    """Nearest x2 + 3x3 / pad 1 as four 2x2 phase convolutions of x [B,H,W,Cin] -> [B,2H,2W,Cout] (pw from pack_conv3x3_up2).  Runs on the
-    halo-resident kernel's phase form only: outside conv_up2_eligible the library refuses (callers ask first and keep conv3x3(upsample=True))."""
+def conv3x3_up2(x: torch.Tensor, pw: PackedWeight, *, tile: int = 14, splits: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Nearest x2 + 3x3 / pad 1 as four 2x2 phase convolutions of x [B,H,W,Cin] -> [B,2H,2W,Cout] (pw from pack_conv3x3_up2).  Runs inside
+    conv_up2_eligible only (tile, splits: conv_up2_config): outside it the library refuses (callers ask first and keep conv3x3(upsample=True)).
+    out: a contiguous fp16 [B,2H,2W,Cout] tensor to write instead of a fresh one."""
     _chk_f16(x, "conv3x3_up2.x")
     B, H, W, c1 = x.shape
     assert pw.up2 and pw.cin == c1, f"conv3x3_up2: needs a pack_conv3x3_up2 weight of {c1} input channels"
-    out = torch.empty((B, 2 * H, 2 * W, pw.N), dtype=F16, device=x.device)
-    d = conv_up2_desc(B, H, W, c1, pw.N)
+    if out is None:
+        out = torch.empty((B, 2 * H, 2 * W, pw.N), dtype=F16, device=x.device)
+    else:
+        _chk_f16(out, "conv3x3_up2.out")
+        assert tuple(out.shape) == (B, 2 * H, 2 * W, pw.N), f"conv3x3_up2: out must be {(B, 2 * H, 2 * W, pw.N)}, got {tuple(out.shape)}"
+    d = conv_up2_desc(B, H, W, c1, pw.N, tile=tile, splits=splits)
     assert d.K == pw.K and d.kpad == pw.kpad
     d.a1, d.wt, d.bias, d.out = _p(x), _p(pw.wt), _p(pw.bias), _p(out)
     _launch_gemm(d, x.device, "af_gemm(conv3x3_up2)", tile, splits)

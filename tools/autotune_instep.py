@@ -37,9 +37,11 @@ def main():
     ap.add_argument("--min-gain", type=float, default=0.02, help="a configuration replaces the table's only if it is this fraction faster in the step")
     ap.add_argument("--min-us", type=float, default=1.0, help="... and saves at least this many microseconds per unit of the workload")
     ap.add_argument("--protect", default="", help="comma-separated logs of earlier runs of this tool: the shapes they tuned are left alone (a training leg must not re-tune the denoise step's shapes)")
+    ap.add_argument("--only", default="", help="semicolon-separated table keys: tune these shapes alone (new launches of a step whose other shapes are settled)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--log", default=None)
     args = ap.parse_args()
+    only = set(filter(None, args.only.split(";")))
     from adaface_dev_amd import SD15_UNET_CONFIG, _lib, ops, rng
     from autotune_gemm import candidate_ok
 
@@ -130,7 +132,7 @@ def main():
             launches[key] = launches.get(key, 0) + 1
             if d.gn_partials:
                 gn_keys.add(key)
-            if key not in shortlist and key not in protected:
+            if key not in shortlist and key not in protected and (not only or key in only):
                 cur = (d.tile, d.splits)                           # what the live path chose for this launch (table, LayerNorm-fold rule, heuristic)
                 res = {}
                 for tile in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17):
