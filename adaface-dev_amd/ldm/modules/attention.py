@@ -18,6 +18,7 @@ Constructor arguments, attribute names (``save_cross_attn_vars``, ``cached_activ
 """
 import math
 import os as _os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -42,6 +43,60 @@ XATTN640_FUSE_MIN_TOKENS = 4096                                   # 64-token wor
 FUSE_XATTN = _os.environ.get("AF_FUSE_XATTN", "1") != "0"      # the C = 320 cross-attention block as ONE launch (af_xattn_fused): on par with the
                                                                 # three launches alone, -0.03 ms per denoise step (csrc/af_xattn_fused.hip); 0 = three launches
 FUSE_FF = _os.environ.get("AF_FUSE_FF", "1") != "0"          # the C = 320 feed-forward as one launch (af_ff_fused); 0 = the two GEMMs (A/B runs)
+FF_FUSE_MIN_ROWS = 24576        # rows from which it is: one workgroup per 128 tokens, worth it once they fill the chip (U-Net batch >= 6 at 64 x 64:
+                                # 121.9 vs 166.5 us at batch 8, 105.1 vs 98.4 at batch 4 -- profiles/r03p_ff_fused.txt)
+LN_FOLD_MIN_ROWS = 1024         # below (the 8 x 8 level) the q | k | v and to_q GEMMs sit on the register-staged 64 x 64 tile, which has no fold, and a 3.8 us
+                                # LayerNorm is cheaper than moving them to a whole-line tile (profiles/r03d_lnfold_runtime_flag.txt: +2.5 .. +4.0 us folded)
+
+
+# ---- routing: which kernels a transformer block launches, decided from integers and flags alone (the switches above are read at call time) ----
+def ln_fold(C, M=None) -> bool:
+    """Whether a LayerNorm over C channels is folded into the projection that consumes it.  M: the rows of a q | k | v or to_q projection, which has a
+    fold from LN_FOLD_MIN_ROWS up only; the GEGLU projection (M = None) has one at every size."""
+    return bool(FOLD_LAYERNORM and C % 64 == 0 and (M is None or M >= LN_FOLD_MIN_ROWS))
+
+
+def xattn_route(C, B, N, L, heads, inner_dim, folded, capture=False, masked=False, chain=False) -> str:
+    """How a cross-attention layer over L context tokens runs: "split" (q projection, attention core, to_out), "fused" (ONE launch: af_xattn_fused) or,
+    where the caller offers the self-attention's to_out in front (``chain``), "chain" (af_xattn_chain).  ``folded``: its LayerNorm is folded into to_q."""
+    if not (FUSE_XATTN and folded and L is not None and L <= 80 and heads == 8 and inner_dim == C and not capture and not masked):
+        return "split"
+    if C == 320 and N % 128 == 0 and B * N >= XATTN_FUSE_MIN_TOKENS:        # 128-token workgroups: once they cover enough of the chip
+        return "chain" if chain and CHAIN_XATTN else "fused"
+    if FUSE_XATTN640 and C == 640 and N % 64 == 0 and B * N >= XATTN640_FUSE_MIN_TOKENS:       # never chained
+        return "fused"
+    return "split"
+
+
+def ff_route(C, M, folded, want_proj_out=False, can_fold_proj_out=False) -> str:
+    """How a feed-forward over [M, C] rows runs: "split" (two GEMMs), "fused" (ONE launch: af_ff_fused) or, where the caller offers the SpatialTransformer's
+    proj_out + residual, with those inside: "chain" (the tail of the one launch: af_ff_chain) or "fold" (folded into the second GEMM's weights)."""
+    want_proj_out = want_proj_out and folded
+    if FUSE_FF and folded and C == 320 and M >= FF_FUSE_MIN_ROWS:
+        return "chain" if want_proj_out and CHAIN_PROJ_OUT else "fused"
+    return "fold" if want_proj_out and FOLD_PROJ_OUT and can_fold_proj_out else "split"
+
+
+class BlockPlan(NamedTuple):
+    """What BasicTransformerBlock.hip launches."""
+    ln12: bool      # norm1 and norm2 run as LayerNorm kernels (else: folded into q | k | v and to_q)
+    ln3: bool       # norm3 runs as a kernel (else: folded into the GEGLU projection)
+    xattn: str      # attn2: "chain" | "fused" | "split" (xattn_route)
+    ff: str         # "chain" | "fused" | "fold" | "split" (ff_route)
+
+    @property
+    def proj_out(self) -> bool:
+        """The caller's proj_out + residual run inside the block: its return value is the SpatialTransformer's output."""
+        return self.ff in ("chain", "fold")
+
+
+def block_plan(C, B, N, L, heads, inner_dim, capture1=False, capture2=False, want_proj_out=False, can_fold_proj_out=False) -> BlockPlan:
+    """The plan of one block on [B * N, C] rows with L context tokens (None: attn2 is a self-attention).  capture1 / capture2: attn1 / attn2 save their
+    cross-attention variables (a capturing attn1 needs its own output: no chain); want_proj_out: the caller is the SpatialTransformer's last block and
+    offers its proj_out; can_fold_proj_out: it has the folded pack (ops.pack_ff_proj_out) for that."""
+    fold12, fold3 = ln_fold(C, B * N), ln_fold(C)
+    return BlockPlan(not fold12, not fold3, xattn_route(C, B, N, L, heads, inner_dim, fold12, capture2, chain=not capture1),
+                     ff_route(C, B * N, fold3, want_proj_out, can_fold_proj_out))
 
 
 def exists(val):
@@ -125,23 +180,12 @@ class FeedForward(nn.Module):
             raise NotImplementedError("dropout > 0 is not supported (SD-1.5 uses 0)")
         self.net = nn.Sequential(GEGLU(dim, inner_dim), nn.Dropout(dropout), Linear(inner_dim, dim_out))
 
-    def ff_fusable(self, M, C, ln) -> bool:
-        """Whether this feed-forward runs as the one-launch C = 320 kernel (af_ff_fused / af_ff_chain)."""
-        return bool(FUSE_FF and ln is not None and C == 320 and M >= 24576)
-
-    def hip(self, x2d, residual=None, ln=None, post=None):
-        """post = (proj_out pack, x_in 2-D, rows per image, gn_cpg, fold): the SpatialTransformer's proj_out + residual run here too (the caller asked
-        BasicTransformerBlock.post_done) -- chained behind the one-launch feed-forward where that runs (af_ff_chain), else folded into the second
-        projection: ``fold()`` is the [W_p W2 | W_p] pack and the GEMM reads [g ; residual]."""
-        if post is not None:
-            pw_p, x_in, rpb, cpg, fold = post
-            if self.ff_fusable(x2d.shape[0], x2d.shape[1], ln):
-                return ops.ff_chain(x2d, self.net[0].packed_ln(ln), self.net[2].packed(), residual, pw_p, x_in, rows_per_batch=rpb, gn_cpg=cpg)
-            return ops.gemm(self.net[0].hip(x2d, ln=ln), fold(), a2=residual, residual=x_in, rows_per_batch=rpb, gn_cpg=cpg)
-        if FUSE_FF and ln is not None and x2d.shape[1] == 320 and x2d.shape[0] >= 24576:
+    def hip(self, x2d, residual=None, ln=None, route=None):
+        """``ln``: the LayerNorm in front, folded into the GEGLU projection (x2d is then un-normalised).  ``route``: "fused" or "split" from the caller's
+        plan; None = decided here (ff_route)."""
+        if (route or ff_route(x2d.shape[1], x2d.shape[0], ln is not None)) == "fused":
             # the 64 x 64 level: LayerNorm, GEGLU projection, output projection and residual as ONE launch (af_ff_fused): the
-            # [tokens, 1280] intermediate never leaves the compute unit.  One workgroup per 128 tokens: worth it once they fill the chip
-            # (U-Net batch >= 6: 121.9 vs 166.5 us at batch 8, 105.1 vs 98.4 at batch 4 -- profiles/r03p_ff_fused.txt)
+            # [tokens, 1280] intermediate never leaves the compute unit
             return ops.ff_fused(x2d, self.net[0].packed_ln(ln), self.net[2].packed(), residual=residual)
         return self.net[2].hip(self.net[0].hip(x2d, ln=ln), residual=residual)
 
@@ -202,51 +246,47 @@ class CrossAttention(nn.Module):
         return self._q_cache_ln.get((self.to_q.weight, ln.weight, ln.bias), lambda: ops.pack_matrix_ln(
             self.to_q.weight, None, ln.weight, ln.bias, ln.eps, self.to_q.weight.device))
 
-    def xattn_fusable(self, C, B, N, L, ln, chain=False) -> bool:
-        """Whether this (cross-attention) layer runs as the one-launch block (af_xattn_fused; ``chain``: af_xattn_chain, C = 320 only)."""
-        if not (FUSE_XATTN and ln is not None and self.heads == 8 and not self.save_cross_attn_vars and L <= 80 and self.inner_dim == C):
-            return False
-        if C == 320:
-            return N % 128 == 0 and B * N >= XATTN_FUSE_MIN_TOKENS
-        return bool(FUSE_XATTN640 and not chain and C == 640 and N % 64 == 0 and B * N >= XATTN640_FUSE_MIN_TOKENS)
+    def _kv(self, context, B):
+        """(k, v^T, k's row stride) of the context: this layer's own k | v projection, unless UNetModel._project_context_all projected all layers' at once."""
+        if self._kv_pre is not None:
+            return self._kv_pre
+        L = context.shape[1]
+        k, vt = ops.gemm(context.reshape(B * L, context.shape[-1]), self._packed_kv(), rows_per_batch=L, split_col=self.inner_dim)
+        return k, vt, self.inner_dim
 
-    def hip(self, x2d, B, N, context=None, keybias=None, residual=None, ln=None, defer_out=False, pre=None):
+    def self_core(self, x2d, B, N, keybias=None, ln=None):
+        """Self-attention up to to_out: ONE q | k | v projection (``ln`` folded in) and softmax(QK^T)V -> (o [B*N, inner_dim], the q | k columns, v^T)."""
+        Ci = self.inner_dim
+        if self.to_k.in_features != self.to_q.in_features:
+            raise RuntimeError("CrossAttention: context is required (context_dim != query_dim)")
+        qk, vt = ops.gemm(x2d, self._packed_qkv() if ln is None else self._packed_qkv_ln(ln), rows_per_batch=N, split_col=2 * Ci)
+        o = ops.attention(qk, qk[:, Ci:], vt, B=B, Nq=N, L=N, heads=self.heads, d=self.dim_head, ldq=2 * Ci, ldk=2 * Ci, keybias=keybias, scale=self.scale)
+        return o, qk, vt
+
+    def hip(self, x2d, B, N, context=None, keybias=None, residual=None, ln=None, route=None):
         """x2d [B*N, C] fp16; context [B, L, Cc] fp16 or None (self-attention); keybias fp32
         [B, roundup(L,64)] or None; residual [B*N, C] added after to_out.  ``ln``: the LayerNorm whose output this layer's query
         (and, for self-attention, key / value) projection consumes -- x2d is then the UN-normalised input and the normalisation is
-        folded into the projection GEMM.  Returns [B*N, C]."""
+        folded into the projection GEMM.  ``route``: "fused" or "split" from the caller's plan; None = decided here (xattn_route).  Returns [B*N, C]."""
         Ci, h, d = self.inner_dim, self.heads, self.dim_head
         if context is None:
-            if self.to_k.in_features != self.to_q.in_features:
-                raise RuntimeError("CrossAttention: context is required (context_dim != query_dim)")
             L = N
-            qk, vt = ops.gemm(x2d, self._packed_qkv() if ln is None else self._packed_qkv_ln(ln), rows_per_batch=N, split_col=2 * Ci)
-            q, k, ldq, ldk = qk, qk[:, Ci:], 2 * Ci, 2 * Ci
+            o, q, vt = self.self_core(x2d, B, N, keybias, ln)
+            k = q[:, Ci:]
         else:
             L = context.shape[1]
-            ldk = Ci
-            if self._kv_pre is not None:                     # projected for all layers at once by UNetModel._project_context_all
-                k, vt, ldk = self._kv_pre
-            else:
-                k, vt = ops.gemm(context.reshape(B * L, context.shape[-1]), self._packed_kv(), rows_per_batch=L, split_col=Ci)
-            if pre is not None:
-                # round 6: the self-attention's output projection + residual chained in front (BasicTransformerBlock.hip decided with xattn_fusable):
-                # pre = (self-attention core output, attn1.to_out pack, the block's input)
-                ao, pw_o1, x0 = pre
-                return ops.xattn_chain(ao, pw_o1, x0, self._packed_q_ln(ln), k, vt, self.to_out[0].packed(), B=B, N=N, L=L, heads=h, scale=self.scale, ldk=ldk)
-            if keybias is None and self.xattn_fusable(x2d.shape[1], B, N, L, ln):
+            k, vt, ldk = self._kv(context, B)
+            if (route or xattn_route(x2d.shape[1], B, N, L, h, Ci, ln is not None, self.save_cross_attn_vars, keybias is not None)) == "fused":
                 # the 64 x 64 level: q projection (norm2 folded in), the 77-key core, to_out and the residual as ONE launch over 128-token tiles
-                # that stay in LDS (af_xattn_fused, tiled form); worth it once the 128-token workgroups cover enough of the chip
+                # that stay in LDS (af_xattn_fused, tiled form)
                 return ops.xattn_fused(x2d, self._packed_q_ln(ln), k, vt, self.to_out[0].packed(), B=B, N=N, L=L, heads=h, scale=self.scale,
                                        ldk=ldk, residual=residual)
             q = self.to_q.hip(x2d) if ln is None else ops.gemm(x2d, self._packed_q_ln(ln))
-            ldq = Ci
-        o = ops.attention(q, k, vt, B=B, Nq=N, L=L, heads=h, d=d, ldq=ldq, ldk=ldk, keybias=keybias, scale=self.scale)
+            o = ops.attention(q, k, vt, B=B, Nq=N, L=L, heads=h, d=d, ldq=Ci, ldk=ldk, keybias=keybias, scale=self.scale)
         if self.save_cross_attn_vars:
             # attention.py:207-220 -- explicit score / prob only on the (rare) capture path
             out_plain = self.to_out[0].hip(o)
-            qc = q if context is not None else qk[:, :Ci].contiguous()
-            kc = k.contiguous() if context is not None else qk[:, Ci:].contiguous()
+            qc, kc = q[:, :Ci].contiguous(), k.contiguous()        # (self-attention: q and k are column slices of one projection)
             score, prob = ops.attention_scores(qc, kc, B=B, Nq=N, L=L, heads=h, d=d, scale=self.scale)
             rs = math.sqrt(self.scale)
             qcap = (qc.reshape(B, N, Ci).permute(0, 2, 1).float() * rs).contiguous()
@@ -262,8 +302,6 @@ class CrossAttention(nn.Module):
             }
             if residual is None:
                 return out_plain
-        if defer_out and not self.save_cross_attn_vars:
-            return o, self.to_out[0].packed(), residual          # the consumer (the chained cross-attention block) runs to_out + residual itself
         return self.to_out[0].hip(o, residual=residual)
 
     # ---- training mode: row-major q|k|v kept for the flash backward
@@ -338,40 +376,37 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = LayerNorm(dim)
         self.checkpoint = checkpoint
 
-    def hip(self, x2d, B, N, context=None, keybias=None, post=None):
-        """attention.py:242-252 with the three residual adds fused into GEMM epilogues.  post (SpatialTransformer.hip, its LAST block only) = (proj_out pack, x_in 2-D,
-        rows per image, gn_cpg, getter of the folded pack): proj_out + residual run as the tail of the one-launch feed-forward where that runs (af_ff_chain),
-        else folded into the feed-forward's second GEMM (FOLD_PROJ_OUT) -- the return value is then the SpatialTransformer's output and ``post_done(...)`` says so."""
-        if FOLD_LAYERNORM and x2d.shape[1] % 64 == 0:
-            # the LayerNorms do not run as kernels: each is folded into the projection GEMM that consumes it.  Below ~1,000 rows (the
-            # 8 x 8 level) the q | k | v and to_q GEMMs sit on the register-staged 64 x 64 tile, which has no fold, and a 3.8 us LayerNorm
-            # is cheaper than moving them to a whole-line tile (profiles/r03d_lnfold_runtime_flag.txt: +2.5 .. +4.0 us folded)
-            small = x2d.shape[0] < 1024
-            if (CHAIN_XATTN and not small and context is not None and not self.attn1.save_cross_attn_vars 
-                    and self.attn2.xattn_fusable(x2d.shape[1], B, N, context.shape[1], self.norm2, chain=True)):
-                # the 64 x 64 level: attn1's to_out + residual run as phase 0 of the one-launch cross-attention block (af_xattn_chain)
-                pre = self.attn1.hip(x2d, B, N, None, keybias, residual=x2d, ln=self.norm1, defer_out=True)
-                x2 = self.attn2.hip(None, B, N, context, None, residual=None, ln=self.norm2, pre=pre)
-                return self.ff.hip(x2, residual=x2, ln=self.norm3, post=post if self.post_done(x2d.shape[0], x2d.shape[1], post) else None)
-            x1 = self.attn1.hip(self.norm1.hip(x2d) if small else x2d, B, N, None, keybias, residual=x2d, ln=None if small else self.norm1)
-            x2 = self.attn2.hip(self.norm2.hip(x1) if small else x1, B, N, context, None, residual=x1, ln=None if small else self.norm2)
-            return self.ff.hip(x2, residual=x2, ln=self.norm3, post=post if self.post_done(x2d.shape[0], x2d.shape[1], post) else None)
-        x1 = self.attn1.hip(self.norm1.hip(x2d), B, N, None, keybias, residual=x2d)
-        x2 = self.attn2.hip(self.norm2.hip(x1), B, N, context, None, residual=x1)
-        return self.ff.hip(self.norm3.hip(x2), residual=x2)
+    def plan(self, C, B, N, context, want_proj_out=False, can_fold_proj_out=False) -> BlockPlan:
+        """block_plan of this block's layers on [B * N, C] rows."""
+        return block_plan(C, B, N, None if context is None else context.shape[1], self.attn2.heads, self.attn2.inner_dim, self.attn1.save_cross_attn_vars,
+                          self.attn2.save_cross_attn_vars, want_proj_out, can_fold_proj_out)
 
-    def post_done(self, M, C, post) -> bool:
-        """Whether ``hip(..., post=post)`` on [M, C] rows runs the caller's proj_out + residual itself: as the tail of the one-launch feed-forward
-        (af_ff_chain, C = 320), or, where the feed-forward is two GEMMs, folded into the second one (FOLD_PROJ_OUT; post[4] is then the pack's getter)."""
-        if post is None or not FOLD_LAYERNORM or C % 64 != 0:
-            return False
-        if self.ff.ff_fusable(M, C, self.norm3):
-            return CHAIN_PROJ_OUT
-        return bool(FOLD_PROJ_OUT and post[4] is not None)
+    def hip(self, x2d, B, N, context=None, keybias=None, plan=None, pw_out=None, x_in=None, gn_cpg=0):
+        """attention.py:242-252 with the three residual adds fused into GEMM epilogues, launched as ``plan`` says (default: self.plan(...), no proj_out).
+        Where plan.proj_out (SpatialTransformer.hip, its LAST block only), the SpatialTransformer's proj_out + residual run here too and the return value is
+        its output: x_in [B*N, C] is its input, gn_cpg the channels per group of the GroupNorm partials to leave, pw_out its proj_out pack (plan.ff ==
+        "chain") or ff.net[2] with proj_out folded behind it (ops.pack_ff_proj_out; "fold": one K-concatenated GEMM over [g ; x2])."""
+        p = plan or self.plan(x2d.shape[1], B, N, context)
+        a1, a2, ff = self.attn1, self.attn2, self.ff
+        ln1, ln2, ln3 = (None if p.ln12 else self.norm1), (None if p.ln12 else self.norm2), (None if p.ln3 else self.norm3)
+        if p.xattn == "chain":
+            # the 64 x 64 level: attn1's to_out + residual run as phase 0 of the one-launch cross-attention block (af_xattn_chain)
+            o, pw_o1 = a1.self_core(x2d, B, N, keybias, ln1)[0], a1.to_out[0].packed()
+            k, vt, ldk = a2._kv(context, B)
+            x2 = ops.xattn_chain(o, pw_o1, x2d, a2._packed_q_ln(ln2), k, vt, a2.to_out[0].packed(), B=B, N=N, L=context.shape[1], heads=a2.heads,
+                                 scale=a2.scale, ldk=ldk)
+        else:
+            x1 = a1.hip(x2d if ln1 else self.norm1.hip(x2d), B, N, None, keybias, residual=x2d, ln=ln1)
+            x2 = a2.hip(x1 if ln2 else self.norm2.hip(x1), B, N, context, None, residual=x1, ln=ln2, route=p.xattn)
+        if p.ff == "chain":
+            return ops.ff_chain(x2, ff.net[0].packed_ln(ln3), ff.net[2].packed(), x2, pw_out, x_in, rows_per_batch=N, gn_cpg=gn_cpg)
+        if p.ff == "fold":
+            return ops.gemm(ff.net[0].hip(x2, ln=ln3), pw_out, a2=x2, residual=x_in, rows_per_batch=N, gn_cpg=gn_cpg)
+        return ff.hip(x2 if ln3 else self.norm3.hip(x2), residual=x2, ln=ln3, route=p.ff)
 
     def hip_train(self, x2d, B, N, context=None, keybias=None):
-        if FOLD_LAYERNORM and x2d.shape[1] % 64 == 0 and x2d.shape[0] >= 1024:
-            # the LayerNorm outputs are not needed by the backward (it re-normalises from the saved inputs): fold them as in hip()
+        if ln_fold(x2d.shape[1], x2d.shape[0]):
+            # the LayerNorm outputs are not needed by the backward (it re-normalises from the saved inputs): fold them as in hip(), all three or none
             x1, s1 = self.attn1.hip_train(x2d, B, N, None, keybias, residual=x2d, ln=self.norm1)
             x2, s2 = self.attn2.hip_train(x1, B, N, context, None, residual=x1, ln=self.norm2)
             x3, hp = self.ff.hip_train(x2, residual=x2, ln=self.norm3)
@@ -454,18 +489,18 @@ class SpatialTransformer(nn.Module):
         # the block's output feeds the next GroupNorm(32) (a ResBlock's first norm or the output norm) when it is not concatenated first: leave
         # the partial statistics with it (ops.GnPartials)
         cpg = Cn // 32 if Cn % 32 == 0 else 0
-        last = len(self.transformer_blocks) - 1
-        post = (self.proj_out.packed(), x.reshape(B * N, Cn), N, cpg, self._packed_ff_proj_out)
-        chained = False
+        pw_out, x_in = self.proj_out.packed(), x.reshape(B * N, Cn)
+        plan = None
         for i, block in enumerate(self.transformer_blocks):
             block.attn2.infeat_size = (H, W)
-            if i == last and block.post_done(B * N, y.shape[1], post):
-                # proj_out + residual inside the last block's feed-forward: the tail of its one-launch form (C = 320, the 64 x 64 level: af_ff_chain), or
-                # folded into its second projection's weights (C = 640 / 1280: one K = 5 C GEMM over [g ; x2], ops.pack_ff_proj_out)
-                y, chained = block.hip(y, B, N, context, kb, post=post), True
-            else:
+            if i + 1 < len(self.transformer_blocks):
                 y = block.hip(y, B, N, context, kb)
-        out = y if chained else ops.gemm(y, self.proj_out.packed(), residual=x.reshape(B * N, Cn), rows_per_batch=N, gn_cpg=cpg)
+                continue
+            # the last block is offered proj_out + residual: inside its feed-forward as the tail of the one-launch form (C = 320, the 64 x 64 level: af_ff_chain),
+            # or folded into its second projection's weights (C = 640 / 1280: one K = 5 C GEMM over [g ; x2]); its plan, made once, says which, or neither
+            plan = block.plan(y.shape[1], B, N, context, want_proj_out=True, can_fold_proj_out=True)
+            y = block.hip(y, B, N, context, kb, plan, self._packed_ff_proj_out() if plan.ff == "fold" else pw_out, x_in, cpg)
+        out = y if plan is not None and plan.proj_out else ops.gemm(y, pw_out, residual=x_in, rows_per_batch=N, gn_cpg=cpg)
         out4 = out.reshape(B, H, W, Cn)
         if hasattr(out, "_gn_partials"):
             out4._gn_partials = out._gn_partials      # a view: same storage address and version counter (ops.partials_of)

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from .attention import FOLD_LAYERNORM, FeedForward, Normalize
+from .attention import FeedForward, Normalize, ln_fold
 from .diffusionmodules.util import LayerNorm, Linear, _PackCache
 
 MAX_FRAMES = ops.TEMPORAL_ATTN_MAX_FRAMES
@@ -85,7 +85,7 @@ class TemporalAttention(nn.Module):
 
     def hip(self, h, ln, B, F, HW):
         """h [B*F*HW, C] fp16 (un-normalised) -> h + to_out(attention)."""
-        fold = FOLD_LAYERNORM and h.shape[1] % 64 == 0 and h.shape[0] >= 1024           # as BasicTransformerBlock.hip: no fold on the small tiles
+        fold = ln_fold(h.shape[1], h.shape[0])
         qkv = ops.gemm(h if fold else ln.hip(h), self._packed_qkv(ln if fold else None), rowbias=self._pe_rowbias(B, F), rows_per_batch=HW)
         o = ops.temporal_attention(qkv, B=B, F=F, HW=HW, heads=self.heads, d=self.dim_head, scale=self.dim_head ** -0.5)
         return self.to_out[0].hip(o, residual=h)
@@ -102,9 +102,8 @@ class TemporalTransformerBlock(nn.Module):
     def hip(self, h, B, F, HW):
         for attn, ln in zip(self.attention_blocks, self.norms):
             h = attn.hip(h, ln, B, F, HW)
-        if FOLD_LAYERNORM and h.shape[1] % 64 == 0:
-            return self.ff.hip(h, residual=h, ln=self.ff_norm)
-        return self.ff.hip(self.ff_norm.hip(h), residual=h)
+        ln = self.ff_norm if ln_fold(h.shape[1]) else None
+        return self.ff.hip(h if ln else self.ff_norm.hip(h), residual=h, ln=ln)
 
 
 class TemporalTransformer(nn.Module):

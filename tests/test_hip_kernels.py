@@ -1086,7 +1086,8 @@ def test_xattn_fused_c320(dev, B, N, L, with_ln, with_res, ld_extra, C):
         old640, A.FUSE_XATTN640, min640, A.XATTN640_FUSE_MIN_TOKENS = A.FUSE_XATTN640, True, A.XATTN640_FUSE_MIN_TOKENS, 64
         try:
             if with_ln and A.FUSE_XATTN:
-                assert m.xattn_fusable(C, B, N, L, ln) and not m.xattn_fusable(C, B, N, L, ln, chain=True)
+                route = [A.xattn_route(C, B, N, L, m.heads, m.inner_dim, ln is not None, m.save_cross_attn_vars, chain=chain) for chain in (False, True)]
+                assert route == ["fused", "fused"]            # one launch, and never the chained form at C = 640
                 out1 = m.hip(x.to(dev), B, N, context=ctx.to(dev), residual=None if res is None else res.to(dev), ln=ln)
                 assert torch.equal(out1, out)
         finally:
