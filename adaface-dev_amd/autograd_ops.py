@@ -75,8 +75,16 @@ class LayerNormFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         dx = ops.layernorm_bwd(x, g32, dy, ctx.eps) if need[0] else None
         dg = db = None
-        if (need[1] or need[2]) and x.numel() // x.shape[-1] <= 2048 and x.shape[-1] <= 1536:
-            dg, db = ops.layernorm_param_grads(x, dy, ctx.eps)               # row statistics + one column pass (af_layernorm_param_grads)
+        C = x.shape[-1]
+        rows = x.numel() // C
+        if (need[1] or need[2]) and C <= 1536:
+            # row statistics + one column pass (af_layernorm_param_grads), 2048 rows per call (its limit), the slabs' fp32 sums added.  Taller
+            # inputs used to take the branch below, whose x_hat is ROUNDED TO fp16 before the column sum: dgamma rel-L2 2.7e-4 against fp64 at
+            # 2049 rows where this path gives 1.9e-7 at 2048 (tests/test_hip_autograd_nodes.py)
+            xr, dyr = x.reshape(rows, C), dy.reshape(rows, C)
+            for r0 in range(0, rows, 2048):
+                g, b = ops.layernorm_param_grads(xr[r0:r0 + 2048], dyr[r0:r0 + 2048], ctx.eps)
+                dg, db = (g, b) if dg is None else (dg + g, db + b)
             dg = dg.to(ctx.pdtype) if need[1] else None
             db = db.to(ctx.pdtype) if need[2] else None
         else:
@@ -211,12 +219,21 @@ class MatmulNTFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         amax = dc.abs().amax().float().clamp_min(1e-30)
         scale = torch.exp2(torch.floor(torch.log2(256.0 / amax)))
-        d16 = (dc.float() * scale).to(F16).contiguous()
+        d16 = (dc.float() * scale).to(F16)
+        btk = bt16.t()                                                        # [K, N]: dC's N columns are the reduction of dA
+        N = d16.shape[1]
+        n8 = round_up(N, 8)
+        if n8 != N:
+            # the forward takes N % 4 == 0, but dC is the A operand here and af_gemm wants A rows of whole 16-byte groups (c1 % 8 == 0): N % 8 == 4
+            # was refused with AF_E_BADARG.  Zero columns add nothing to dA; the rows they add to dBt are dropped below
+            d16 = torch.nn.functional.pad(d16, (0, n8 - N))
+            btk = torch.nn.functional.pad(btk, (0, n8 - N))
+        d16 = d16.contiguous()
         da = dbt = None
         if need[0]:
-            da = (ops.gemm(d16, ops.pack_matrix(bt16.t(), None, dc.device), out_f32=True) / scale).to(ctx.dtypes[0])
+            da = (ops.gemm(d16, ops.pack_matrix(btk, None, dc.device), out_f32=True) / scale).to(ctx.dtypes[0])
         if need[1]:
-            dbt = (wgrad(d16, a16) / scale).to(ctx.dtypes[1])
+            dbt = (wgrad(d16, a16)[:N] / scale).to(ctx.dtypes[1])
         return da, dbt
 
 
