@@ -80,6 +80,16 @@ ldm/modules/diffusionmodules/controlnet.py).  ``control_image`` is a PIL image, 
 the sampling call only, and the sampler's per-step callback switches it by the guidance window.  Without ``control_image`` every path is
 the call as it was.
 
+``forward(..., ip_adapter_image=img | ip_adapter_face_id=emb, ip_adapter_scale=1.0, ip_guidance_start=0.0, ip_guidance_end=1.0)``
+(INTEGRATION.md "IP-Adapter") adds an image prompt on all three pipelines, under all three samplers, with ``num_frames``, ``control_image``
+and both passes of ``hires_size``, with an IP-Adapter or IP-Adapter-FaceID (``ip_adapter=`` / ``ip_image_encoder=`` at construction or
+``load_ip_adapter``: an ``IPAdapter`` or a local published file / state dict; adaface/ip_adapter.py).  ``ip_adapter_image`` is a PIL image,
+a path, or uint8 ``[H, W, 3]`` / ``[B, H, W, 3]``, 1 (shared) or one per sampled row; for a FaceID adapter the id is extracted from it by the
+``face_id_extractor``, or given as ``ip_adapter_face_id`` fp ``[1 | rows, 512]``.  The tokens are computed once, the adapter sits on the
+U-Net during the sampling call only, and the sampler's per-step callback switches it by its guidance window.  A FaceID file's LoRA is fused
+into the U-Net's weights while the adapter is loaded (``unload_ip_adapter`` restores them).  Without these arguments every path is the call
+as it was.
+
 ``forward(photo, ..., mask_image="face", crop_padding=0.5)`` (``inpaint`` only; INTEGRATION.md "Repainting faces in a photo") repaints
 the faces of ONE photo of any size (a PIL image, a path or a uint8 array) and hands back the same photo: ``face_detector`` (any callable
 with ``FaceIDExtractor``'s detector contract, e.g. a ``RetinaFaceDetector``; by default the ``face_id_extractor``'s) finds the faces,
@@ -261,7 +271,7 @@ class AdaFaceWrapper(nn.Module):
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
                  lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None, face_detector=None, motion_module_path=None,
-                 beta_schedule="linear", upscaler=None, face_restorer=None, controlnet=None):
+                 beta_schedule="linear", upscaler=None, face_restorer=None, controlnet=None, ip_adapter=None, ip_image_encoder=None):
         super().__init__()
         if pipeline_name not in ("text2img", "img2img", "inpaint", None):
             raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img, img2img and inpaint paths (and None = face "
@@ -320,6 +330,8 @@ class AdaFaceWrapper(nn.Module):
         self.__dict__["face_restorer"] = None     # a gfpgan.FaceRestorer (load_face_restorer) for forward(restore_faces=True); not a submodule
         self.__dict__["motion_module"] = None     # a MotionModule (load_motion_module); not a submodule: it is on the U-Net only inside forward(num_frames=F)
         self.__dict__["controlnet"] = None        # a ControlNet (load_controlnet); not a submodule: it is on the U-Net only inside forward(control_image=...)
+        self.__dict__["ip_adapter"] = None        # an IPAdapter (load_ip_adapter); not a submodule: it is on the U-Net only inside forward(ip_adapter_image= / ip_adapter_face_id=)
+        self.__dict__["ip_image_encoder"] = None  # the CLIP ViT-H/14 VisionTransformer of a kind="clip" adapter; not a submodule
         self.vae = vae
         self.img_prompt_embs = None
         self._lcm_lora = None                 # (read_unet_lora dict, scale) of the fused LoRA
@@ -339,6 +351,10 @@ class AdaFaceWrapper(nn.Module):
             self.load_face_restorer(face_restorer)
         if controlnet is not None:
             self.load_controlnet(controlnet)
+        if ip_adapter is not None:
+            self.load_ip_adapter(ip_adapter, ip_image_encoder)
+        elif ip_image_encoder is not None:
+            raise ValueError("ip_image_encoder is given without ip_adapter")
 
     # ------------------------------------------------------------------ checkpoints
     def load_base_model(self, base_model_path):
@@ -428,27 +444,132 @@ class AdaFaceWrapper(nn.Module):
             raise ValueError(f"control images must be exactly 8 x the latent size, {8 * latent_hw[1]} x {8 * latent_hw[0]} pixels, got "
                              f"{images.shape[2]} x {images.shape[1]} (nothing is resized)")
 
-    def _sample_controlled(self, control, n_steps, call):
+    def _sample_controlled(self, control, n_steps, call, ip=None):
         """``call(**kw)`` runs one of the sampler's loops.  With ``control`` = (images uint8, scale, start, end) the ControlNet is on the
         U-Net around that call only: the hints are encoded once, and the sampler's per-step callback switches the control off and on by the
-        guidance window (active at step i of n iff i / n >= start and (i + 1) / n <= end).  Without it this is ``call()``: the sampler is
+        guidance window (active at step i of n iff i / n >= start and (i + 1) / n <= end).  With ``ip`` = (cond tokens, uncond tokens, scale,
+        start, end) the IP-Adapter is on the U-Net in the same way, under its own window.  Without either this is ``call()``: the sampler is
         called exactly as before."""
-        if control is None:
+        if control is None and ip is None:
             return call()
         from ..ldm.modules.diffusionmodules.controlnet import guidance_window_active
-        images, scale, start, end = control
         unet = self.ldm.model.diffusion_model
-        cn = self.controlnet.to(self.device)
-        unet.set_control(cn, cn.hint_features(images.to(self.device)), scale)
 
         def switch(i):
-            unet.set_control_active(i < n_steps and guidance_window_active(i, n_steps, start, end))
+            if control is not None:
+                unet.set_control_active(i < n_steps and guidance_window_active(i, n_steps, control[2], control[3]))
+            if ip is not None:
+                unet.set_ip_adapter_active(i < n_steps and guidance_window_active(i, n_steps, ip[3], ip[4]))
 
         try:
+            if control is not None:
+                cn = self.controlnet.to(self.device)
+                unet.set_control(cn, cn.hint_features(control[0].to(self.device)), control[1])
+            if ip is not None:
+                unet.set_ip_adapter(self.ip_adapter, ip[0], ip[1], ip[2])
             switch(0)
             return call(callback=lambda i: switch(i + 1))                # the callback runs behind step i
         finally:
             unet.set_control(None)
+            unet.set_ip_adapter(None)
+
+    # ------------------------------------------------------------------ IP-Adapter (adaface/ip_adapter.py; INTEGRATION.md "IP-Adapter")
+    def load_ip_adapter(self, path_or_obj, image_encoder=None, lora_scale=1.0):
+        """An IP-Adapter (``kind="clip"``) or IP-Adapter-FaceID (``kind="faceid"``) for ``forward(..., ip_adapter_image= / ip_adapter_face_id=)``:
+        an ``IPAdapter``, or a local ``.bin`` / ``.safetensors`` file or its state dict, loaded strictly for this wrapper's U-Net.
+        ``image_encoder``: the CLIP ViT-H/14 vision tower of a ``clip`` adapter -- a ``VisionTransformer``, or a local file / state dict in
+        transformers' ``CLIPVisionModelWithProjection`` layout.  A FaceID file's LoRA is fused into the U-Net here (``lora_scale``) and
+        unfused by ``unload_ip_adapter``.  Nothing is downloaded."""
+        from . import ip_adapter as IP
+        from ..evaluation import vit
+        if self.ldm is None:
+            raise RuntimeError("pipeline_name=None builds the face encoder only: there is no U-Net to put an IP-Adapter on")
+        if self.ip_adapter is not None:
+            self.unload_ip_adapter()
+        unet = self.ldm.model.diffusion_model
+        ad = path_or_obj
+        if not isinstance(ad, IP.IPAdapter):
+            cfg = dict(model_channels=unet.model_channels, num_res_blocks=unet.num_res_blocks, attention_resolutions=unet.attention_resolutions,
+                       channel_mult=unet.channel_mult, num_heads=unet.num_heads, context_dim=unet._cross_attn_layers()[0].to_k.in_features)
+            ad = IP.load_ip_adapter(ad, cfg)
+        unet.check_ip_adapter(ad)                                # refuses widths or a layer count that do not match this U-Net
+        enc = image_encoder
+        if enc is not None and not isinstance(enc, vit.VisionTransformer):
+            enc = vit.load_clip_vision(enc)
+        if enc is not None and enc.feature_dim != ad.embed_dim:
+            raise ValueError(f"the image encoder's features are {enc.feature_dim} wide, the adapter's image_proj reads {ad.embed_dim}")
+        ad.fuse(self.ldm.model, lora_scale)
+        self.__dict__["ip_adapter"], self.__dict__["ip_image_encoder"] = ad, enc
+        return ad
+
+    def unload_ip_adapter(self):
+        ad = self.ip_adapter
+        self.__dict__["ip_adapter"], self.__dict__["ip_image_encoder"] = None, None
+        if ad is not None:
+            ad.unfuse()
+        if self.ldm is not None:
+            self.ldm.model.diffusion_model.set_ip_adapter(None)
+
+    def _check_ip(self, image, face_id, scale, start, end, rows):
+        """The refusals of forward(ip_adapter_image= / ip_adapter_face_id=) (INTEGRATION.md "IP-Adapter"), all before any GPU work.  Returns
+        ("images", [uint8 arrays]) or ("ids", fp32 [1 | rows, 512])."""
+        ad = self.ip_adapter
+        if ad is None:
+            raise ValueError("ip_adapter_image / ip_adapter_face_id is given but no IP-Adapter is loaded (ip_adapter= at construction / load_ip_adapter)")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not np.isfinite(scale):
+            raise ValueError(f"ip_adapter_scale must be a finite number, got {scale!r}")
+        ok = all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (start, end))
+        if not ok or not 0 <= start < end <= 1:
+            raise ValueError(f"the IP-Adapter guidance window needs 0 <= ip_guidance_start < ip_guidance_end <= 1, got {start!r}, {end!r}")
+        extractor = getattr(self.id2ada_prompt_encoder, "face_id_extractor", None)
+        if face_id is not None:
+            if ad.kind != "faceid":
+                raise ValueError(f"ip_adapter_face_id is given but the loaded adapter is of kind {ad.kind!r}: it takes ip_adapter_image")
+            if image is not None:
+                raise ValueError("give ip_adapter_face_id or ip_adapter_image, not both")
+            if not torch.is_tensor(face_id) or not face_id.is_floating_point() or face_id.dim() != 2 or face_id.shape[1] != ad.embed_dim:
+                raise ValueError(f"ip_adapter_face_id must be a floating-point tensor [1 | {rows}, {ad.embed_dim}], got "
+                                 f"{(face_id.dtype, tuple(face_id.shape)) if torch.is_tensor(face_id) else type(face_id).__name__}")
+            if face_id.shape[0] not in (1, rows):
+                raise ValueError(f"ip_adapter_face_id: 1 embedding (shared) or one per sampled row ({rows}) expected, got {face_id.shape[0]}")
+            return "ids", face_id
+        if ad.kind == "clip" and self.ip_image_encoder is None:
+            raise ValueError("the loaded IP-Adapter is of kind 'clip' and needs an image encoder (ip_image_encoder= at construction / "
+                             "load_ip_adapter(..., image_encoder=...))")
+        if ad.kind == "faceid" and extractor is None:
+            raise ValueError("the loaded adapter is of kind 'faceid': it takes ip_adapter_face_id, or ip_adapter_image with a face_id_extractor "
+                             "at construction")
+        items = list(image) if isinstance(image, (list, tuple)) else [image]
+        flat = []
+        for im in items:
+            if torch.is_tensor(im) and im.dtype == torch.uint8 and im.dim() == 4 and im.shape[3] == 3:
+                flat.extend(im.cpu().numpy())
+            elif torch.is_tensor(im) and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3:
+                flat.append(im.cpu().numpy())
+            elif isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 4 and im.shape[3] == 3:
+                flat.extend(im)
+            elif torch.is_tensor(im):
+                raise ValueError(f"ip_adapter_image must be a PIL image, a path or uint8 [H, W, 3] / [B, H, W, 3], got {im.dtype} {tuple(im.shape)}")
+            else:
+                flat.append(im)
+        if len(flat) not in (1, rows):
+            raise ValueError(f"ip_adapter_image: 1 image (shared) or one per sampled row ({rows}) expected, got {len(flat)}")
+        return "images", [load_rgb_u8(im) for im in flat]
+
+    def _ip_tokens(self, what, value, rows):
+        """(cond, uncond) image tokens fp16 [rows, T, context_dim], computed once per forward."""
+        ad = self.ip_adapter.to(self.device)
+        if what == "ids":
+            embeds = nn.functional.normalize(value.float(), p=2, dim=-1)
+        elif ad.kind == "faceid":
+            faceless, embeds = self.id2ada_prompt_encoder.face_id_extractor.extract(value, skip_non_faces=False)
+        else:
+            enc = self.ip_image_encoder.to(self.device)
+            embeds = torch.cat([enc.forward_u8(torch.from_numpy(np.ascontiguousarray(im))[None].to(self.device)) for im in value], 0)
+        cond = ad.tokens(embeds)
+        if cond.shape[0] == 1 and rows > 1:
+            cond = cond.expand(rows, -1, -1).contiguous()
+        return cond, ad.uncond_tokens(1).expand(rows, -1, -1).contiguous()
 
     def load_upscaler(self, path_or_net):
         """A Real-ESRGAN upscaler for ``forward(..., upscale=True)`` (adaface/esrgan.py; INTEGRATION.md "Upscaling (Real-ESRGAN)"): an
@@ -671,7 +792,8 @@ class AdaFaceWrapper(nn.Module):
                 repeat_prompt_for_each_encoder=True, verbose=False, mask_image=None, hires_size=None, hires_strength=0.7,
                 hires_steps=None, hires_upscaler="bilinear", crop_padding=None, face_index=None, face_mask_expand=1.3,
                 face_mask_feather=0.25, work_size=None, num_frames=None, upscale=False, restore_faces=False, control_image=None,
-                control_scale=1.0, control_guidance_start=0.0, control_guidance_end=1.0):
+                control_scale=1.0, control_guidance_start=0.0, control_guidance_end=1.0, ip_adapter_image=None, ip_adapter_face_id=None,
+                ip_adapter_scale=1.0, ip_guidance_start=0.0, ip_guidance_end=1.0):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
         if upscale:
@@ -687,6 +809,9 @@ class AdaFaceWrapper(nn.Module):
         if control_image is not None:
             control = (self._check_control(control_image, control_scale, control_guidance_start, control_guidance_end, out_image_count,
                                            hires_size, repaint), float(control_scale), control_guidance_start, control_guidance_end)
+        ip_in = None
+        if ip_adapter_image is not None or ip_adapter_face_id is not None:
+            ip_in = self._check_ip(ip_adapter_image, ip_adapter_face_id, ip_adapter_scale, ip_guidance_start, ip_guidance_end, out_image_count)
         if hires_size is not None:
             hires_hw, hires_steps = self._check_hires(hires_size, hires_strength, hires_steps, hires_upscaler)
         if upscale and self.pipeline_name == "text2img":
@@ -743,13 +868,16 @@ class AdaFaceWrapper(nn.Module):
         sampler = self._sampler()
         cond = (pe, [prompt or ""] * out_image_count, {})
         uncond = None if ne is None else (ne, [negative_prompt or self.negative_prompt] * out_image_count, {})
+        ip = None
+        if ip_in is not None:
+            ip = self._ip_tokens(ip_in[0], ip_in[1], out_image_count) + (float(ip_adapter_scale), ip_guidance_start, ip_guidance_end)
         if self.pipeline_name == "img2img":
             n_run, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
             x_t = self.ldm.img2img_latents(images_u8.to(self.device), out_image_count, t_first, generator=generator,
                                            first_stage_model=self.vae)
             latents, _ = self._sample_controlled(control, n_run, lambda **cb: sampler.sample_img2img(
                 self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond, guidance_scale=guidance_scale,
-                unconditional_conditioning=uncond, generator=generator, **cb))
+                unconditional_conditioning=uncond, generator=generator, **cb), ip)
             return self._to_pil(latents, upscale, restore_faces)
         if inpaint:
             n_run, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
@@ -764,7 +892,7 @@ class AdaFaceWrapper(nn.Module):
                                                          first_stage_model=self.vae, from_noise=ref_img_strength == 1)
             latents, _ = self._sample_controlled(control, n_run, lambda **cb: sampler.sample_inpaint(
                 self.num_inference_steps, ref_img_strength, out_image_count, x_start, z, n_fwd, masks.to(self.device), cond,
-                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb))
+                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb), ip)
             if repaint is not None:
                 return self._paste_back(latents, photo, alpha, repaint["rect"], upscale, restore_faces)
             return self._to_pil(latents, upscale, restore_faces)
@@ -774,18 +902,19 @@ class AdaFaceWrapper(nn.Module):
             self.motion_module.to(self.device)
             unet.set_motion(self.motion_module, num_frames)           # around the sampling call only
         try:
-            n_run = len(sampler.timesteps(self.num_inference_steps)) if control is not None else None
+            n_run = len(sampler.timesteps(self.num_inference_steps)) if control is not None or ip is not None else None
             latents, _ = self._sample_controlled(control, n_run, lambda **cb: sampler.sample(
                 self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise, verbose=False,
-                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb))
+                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb), ip)
         finally:
             if num_frames is not None:
                 unet.set_motion(None)
         if hires_size is not None:
-            _, t_first = sampler.img2img_steps(hires_steps, hires_strength)
+            n_run2, t_first = sampler.img2img_steps(hires_steps, hires_strength)
             x_t = self.ldm.hires_latents(latents, hires_hw, t_first, generator, hires_upscaler)
-            latents, _ = sampler.sample_img2img(hires_steps, hires_strength, out_image_count, x_t, cond, guidance_scale=guidance_scale,
-                                                unconditional_conditioning=uncond, generator=generator)
+            latents, _ = self._sample_controlled(None, n_run2, lambda **cb: sampler.sample_img2img(
+                hires_steps, hires_strength, out_image_count, x_t, cond, guidance_scale=guidance_scale, unconditional_conditioning=uncond,
+                generator=generator, **cb), ip)
         if self.vae is None:
             return latents
         if num_frames is not None:

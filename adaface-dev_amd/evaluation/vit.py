@@ -27,7 +27,10 @@ CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.261302
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 _CLIP_VISION = {"ViT-B/32": dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, patch_size=32, projection_dim=512),
-                "ViT-L/14": dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, patch_size=14, projection_dim=768)}
+                "ViT-L/14": dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, patch_size=14, projection_dim=768),
+                # OpenCLIP's ViT-H/14 as transformers ships it (laion/CLIP-ViT-H-14-laion2B-s32B-b79K, IP-Adapter's image encoder): 80-wide heads, erf-GELU
+                "ViT-H/14": dict(hidden_size=1280, num_hidden_layers=32, num_attention_heads=16, patch_size=14, projection_dim=1024,
+                                 intermediate_size=5120, hidden_act="gelu")}
 # the text tower that goes with each vision tower (openai/CLIP's model table)
 _CLIP_TEXT = {"ViT-B/32": dict(hidden_size=512, num_attention_heads=8, num_hidden_layers=12, intermediate_size=2048),
               "ViT-L/14": dict(hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072)}
@@ -45,8 +48,9 @@ def clip_vision_config(name="ViT-B/32", **overrides):
     post_layernorm -> projection without bias.  CLIP preprocess: Resize(224) bicubic, CenterCrop(224), CLIP mean / std."""
     if name not in _CLIP_VISION:
         raise ValueError(f"clip_vision_config: unknown model {name!r} (known: {sorted(_CLIP_VISION)})")
-    kw = dict(_CLIP_VISION[name], hidden_act="quick_gelu", layer_norm_eps=1e-5, pre_layernorm=True, patch_bias=False, pool="cls_post_ln",
+    kw = dict(hidden_act="quick_gelu", layer_norm_eps=1e-5, pre_layernorm=True, patch_bias=False, pool="cls_post_ln",
               keep_aspect=True, filter="bicubic", mean=CLIP_MEAN, std=CLIP_STD)
+    kw.update(_CLIP_VISION[name])
     kw.update(overrides)
     return _vit_config(**kw)
 
@@ -302,9 +306,13 @@ def _clip_vision_from_hf(sd, what):
     E, p = w.shape[0], w.shape[-1]
     grid = int(round((pos.shape[0] - 1) ** 0.5))
     fc1 = _need(out, "layers.0.mlp.fc1.weight", what)
-    heads = E // 64                                                    # every CLIP vision tower has 64-wide heads (the state dict does not say)
-    cfg = clip_vision_config("ViT-B/32", hidden_size=E, num_hidden_layers=_count(out, r"layers\.(\d+)\."), num_attention_heads=max(heads, 1),
-                             patch_size=p, image_size=grid * p, projection_dim=proj.shape[0], intermediate_size=fc1.shape[0])
+    # the state dict says neither the head count nor the activation: a tower of a known width and patch takes its table entry's (ViT-H/14:
+    # 16 heads of 80, erf-GELU), any other has 64-wide heads and quick-GELU as openai's CLIP towers do
+    known = next((c for c in _CLIP_VISION.values() if c["hidden_size"] == E and c["patch_size"] == p), {})
+    heads = known.get("num_attention_heads", max(E // 64, 1))
+    cfg = clip_vision_config("ViT-B/32", hidden_size=E, num_hidden_layers=_count(out, r"layers\.(\d+)\."), num_attention_heads=heads,
+                             patch_size=p, image_size=grid * p, projection_dim=proj.shape[0], intermediate_size=fc1.shape[0],
+                             hidden_act=known.get("hidden_act", "quick_gelu"))
     return out, cfg
 
 
@@ -343,6 +351,17 @@ def load_clip(path_or_state_dict, vision_heads=None, text_heads=None):
     vision = _strict_load(VisionTransformer(vcfg), vis_sd, what + " (vision tower)")
     text = _strict_load(CLIPTextTower(tcfg), text_sd, what + " (text tower)")
     return vision.eval(), text.eval()
+
+
+def load_clip_vision(path_or_state_dict, heads=None):
+    """-> ``VisionTransformer`` from transformers' ``CLIPVisionModelWithProjection`` layout (``vision_model.*``, ``visual_projection.weight``), e.g.
+    IP-Adapter's ViT-H/14 image encoder; its feature is ``image_embeds``, the projected CLS.  Strict like ``load_clip``; nothing is downloaded."""
+    what = "load_clip_vision"
+    sd = {k: v for k, v in _read_state_dict(path_or_state_dict, what).items() if not k.endswith("position_ids")}
+    vis_sd, vcfg = _clip_vision_from_hf(sd, what)
+    if heads:
+        vcfg.num_attention_heads = heads
+    return _strict_load(VisionTransformer(vcfg), vis_sd, what).eval()
 
 
 _DINO_FB_LAYER = (("norm1.", "layer_norm1."), ("norm2.", "layer_norm2."), ("attn.proj.", "self_attn.out_proj."), ("mlp.fc1.", "mlp.fc1."),

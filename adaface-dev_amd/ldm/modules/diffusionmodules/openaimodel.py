@@ -390,6 +390,7 @@ class UNetModel(nn.Module):
 
         self._assign_emb_slices()
         self.__dict__["_control"] = None         # set_control's state ({"net", "hint", "scale", "expanded", "active"}) while it holds a ControlNet; not a submodule either
+        self.__dict__["_ip"] = None              # set_ip_adapter's state ({"adapter", "rows", "T", "kv", "scale", "active"}) while it holds an IP-Adapter; not a submodule
         self.__dict__["_motion"] = None          # (MotionModule, num_frames) while set_motion holds one; not a submodule: the state dict stays SD-1.5's
 
     # ------------------------------------------------------------------ reference flag plumbing
@@ -544,6 +545,74 @@ class UNetModel(nn.Module):
         if self._control is not None:
             raise NotImplementedError(f"{what} is not built with a ControlNet: unset it (set_control(None)) first")
 
+    # ------------------------------------------------------------------ IP-Adapter (adaface/ip_adapter.py)
+    def check_ip_adapter(self, adapter):
+        """ValueError unless ``adapter``'s to_k_ip / to_v_ip fit this U-Net's cross-attention layers one to one -> those layers."""
+        layers = self._cross_attn_layers()
+        if len(adapter.to_k_ip) != len(layers) or len(adapter.to_v_ip) != len(layers):
+            raise ValueError(f"set_ip_adapter: the adapter has {len(adapter.to_k_ip)} to_k_ip / {len(adapter.to_v_ip)} to_v_ip layers, the U-Net "
+                             f"{len(layers)} cross-attention layers")
+        for j, (m, wk, wv) in enumerate(zip(layers, adapter.to_k_ip, adapter.to_v_ip)):
+            for name, w in (("to_k_ip", wk), ("to_v_ip", wv)):
+                if (w.out_features, w.in_features) != (m.inner_dim, m.to_k.in_features):
+                    raise ValueError(f"set_ip_adapter: {name} of layer {j} maps {w.in_features} -> {w.out_features}, the U-Net's layer "
+                                     f"{m.to_k.in_features} -> {m.inner_dim}")
+        return layers
+
+    def set_ip_adapter(self, adapter, cond_tokens=None, uncond_tokens=None, scale=1.0):
+        """Run ``hip`` with ``adapter``'s (an IPAdapter) decoupled cross-attention: every one of this U-Net's cross-attention layers adds
+        ``scale`` x the softmax over the image tokens to its text attention (af_ip_attention_add, one launch per layer).  ``cond_tokens`` /
+        ``uncond_tokens``: fp16 [rows, T, context_dim] from ``adapter.image_proj``.  Both sets are projected HERE, once, for all layers by ONE
+        GEMM over the adapter's stacked [all to_k_ip | all to_v_ip] weights; a step only adds the launches.  A batch of ``rows`` runs the cond
+        tokens, a batch of 2 x rows cond then uncond (the samplers' order, sampling.py::_eps); any other batch is a ValueError.  A ControlNet
+        set beside it sees the text only.  ``None`` restores the plain walk exactly, the one-launch routes included."""
+        if adapter is None:
+            self.__dict__["_ip"] = None
+            return
+        layers = self.check_ip_adapter(adapter)
+        cc = layers[0].to_k.in_features
+        for name, t in (("cond_tokens", cond_tokens), ("uncond_tokens", uncond_tokens)):
+            if not torch.is_tensor(t) or t.dtype != F16 or t.dim() != 3 or t.shape[0] < 1 or t.shape[2] != cc or not 1 <= t.shape[1] <= ops.IP_ATTN_MAX_TOKENS:
+                raise ValueError(f"set_ip_adapter: {name} must be fp16 [rows, 1 <= T <= {ops.IP_ATTN_MAX_TOKENS}, {cc}], got "
+                                 f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+        if cond_tokens.shape != uncond_tokens.shape:
+            raise ValueError(f"set_ip_adapter: cond_tokens are {tuple(cond_tokens.shape)}, uncond_tokens {tuple(uncond_tokens.shape)}")
+        scale = float(scale)
+        if scale != scale or scale in (float("inf"), float("-inf")):
+            raise ValueError(f"set_ip_adapter: scale must be finite, got {scale}")
+        rows, T, _ = cond_tokens.shape
+        pack = adapter.packed_kv()                                                # [all to_k_ip | all to_v_ip], packed once per weight version
+        kv = ops.gemm(torch.cat([cond_tokens, uncond_tokens], 0).reshape(2 * rows * T, cc).contiguous(), pack)
+        self.__dict__["_ip"] = {"adapter": adapter, "rows": rows, "T": T, "kv": kv.reshape(2 * rows, T, kv.shape[1]), "scale": scale, "active": True}
+
+    def set_ip_adapter_active(self, active):
+        """Switch the IP-Adapter that is set off or on between two steps (a guidance window) without dropping its projected tokens; while it
+        is off, ``hip`` is the plain walk.  Everything ``_refuse_ip`` refuses stays refused until ``set_ip_adapter(None)``."""
+        if self._ip is None:
+            raise ValueError("set_ip_adapter_active: no IP-Adapter is set")
+        self._ip["active"] = bool(active)
+
+    def _refuse_ip(self, what):
+        if self._ip is not None:
+            raise NotImplementedError(f"{what} is not built with an IP-Adapter: unset it (set_ip_adapter(None)) first")
+
+    def _place_ip(self, B):
+        """Hand every cross-attention layer its slice of the projected image tokens for a batch of B rows -> the layers to clear afterwards."""
+        ip = self._ip
+        if ip is None or not ip["active"]:
+            return []
+        if B not in (ip["rows"], 2 * ip["rows"]):
+            raise ValueError(f"the batch ({B}) is neither the image tokens' rows ({ip['rows']}: cond) nor twice that (cond, then uncond)")
+        layers = self._cross_attn_layers()
+        kv = ip["kv"][:B]
+        sc = kv.shape[2] // 2
+        off = 0
+        for m in layers:
+            c = m.inner_dim
+            m._ip_pre = (kv[:, :, off:off + c], kv[:, :, sc + off:sc + off + c], ip["scale"])
+            off += c
+        return layers
+
     def _control_hint(self, B, hw):
         """The hint features for a batch of B rows (row b: hint b % B0), expanded once per batch size and kept."""
         ctrl = self._control
@@ -582,13 +651,19 @@ class UNetModel(nn.Module):
     def hip(self, x_nhwc, timesteps, context, img_mask=None, capture_layers=()):
         """x_nhwc [B,H,W,8] fp16 (4 latent channels + zero pad), timesteps int64 [B],
         context [B,L,ctx] fp16 -> (eps [B,H,W,out_channels] fp16, captured activations)."""
+        if capture_layers:
+            self._refuse_ip("capturing cross-attention activations")
         emb = self._embed(timesteps)   # SiLU(emb) (its only consumers are the emb_layers) + all 22 projections
         kv_layers = self._project_context_all(context)
+        ip_layers = []
         try:
+            ip_layers = self._place_ip(x_nhwc.shape[0])
             return self._hip_blocks(x_nhwc, emb, context, img_mask, capture_layers, timesteps)
         finally:
             for m in kv_layers:
                 m._kv_pre = None
+            for m in ip_layers:
+                m._ip_pre = None
 
     def _cross_attn_layers(self):
         out = []
@@ -676,6 +751,7 @@ class UNetModel(nn.Module):
         leaves them for those layers."""
         self._refuse_motion("the trunk cache (hip_tail)")
         self._refuse_control("the trunk cache (hip_tail)")
+        self._refuse_ip("the trunk cache (hip_tail)")
         h, skips = trunk
         emb = self._embed(timesteps)
         kv_layers = self._project_context_all(context)
@@ -708,6 +784,7 @@ class UNetModel(nn.Module):
         """Forward that keeps the activations the backward needs.  -> (eps [B,H,W,out_channels], saved)."""
         self._refuse_motion("hip_train")
         self._refuse_control("hip_train")
+        self._refuse_ip("hip_train")
         emb = self._embed(timesteps)
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
@@ -727,6 +804,7 @@ class UNetModel(nn.Module):
         -> (h, [the skips those blocks will pop, in pop order], saved)."""
         self._refuse_motion("hip_train_trunk")
         self._refuse_control("hip_train_trunk")
+        self._refuse_ip("hip_train_trunk")
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
         for module in self.input_blocks:
@@ -747,6 +825,7 @@ class UNetModel(nn.Module):
         nothing saved -- up to the last ``n_tail`` decoder blocks.  -> (h, [the skips those blocks pop, in pop order])."""
         self._refuse_motion("the trunk cache (hip_trunk)")
         self._refuse_control("the trunk cache (hip_trunk)")
+        self._refuse_ip("the trunk cache (hip_trunk)")
         kv_layers = self._project_context_all(context)
         try:
             hs = []
@@ -832,6 +911,7 @@ class UNetModel(nn.Module):
             from .capture_graph import unet_forward_captured
             self._refuse_motion("the captured / score-rewrite path")
             self._refuse_control("the captured / score-rewrite path")
+            self._refuse_ip("the captured / score-rewrite path")
             if extra_info is None:
                 raise ValueError("extra_info must be a dict on the capture / score-rewrite path")
             if capture:
@@ -843,6 +923,7 @@ class UNetModel(nn.Module):
         if trainable:
             self._refuse_motion("training")
             self._refuse_control("training")
+            self._refuse_ip("training")
             gs = float((extra_info or {}).get("res_hidden_states_gradscale", 1) or 1)
             lora = (extra_info or {}).get("_ffn_lora_adapters")           # set by UNetWrapper when use_ffn_lora is on
             return _UNetFunction.apply(self, x, timesteps, context, img_mask, gs, lora, *[t[3] for t in lora_param_order(lora)])

@@ -1303,6 +1303,29 @@ def temporal_attention(qkv, *, B: int, F: int, HW: int, heads: int, d: int, scal
     return o
 
 
+IP_ATTN_MAX_TOKENS = 64           # af_ip_attention_add: 1 <= T <= 64 image tokens, head dim % 8 == 0 in 8 .. 160
+
+
+def ip_attention_add(o, q, k, v, *, B: int, N: int, heads: int, d: int, ip_scale: float, scale=None):
+    """IP-Adapter's decoupled cross-attention, in place: o [B*N, >= heads*d] += ip_scale * softmax(scale q k^T) v over the T image tokens of
+    each batch item, summed with o in fp32 and rounded once.  q [B*N, >= heads*d] token rows; k, v [B, T, heads*d] fp16 views with contiguous
+    channels (any row / batch stride that is a multiple of 8: a column slice of a stacked projection, or ``expand``-ed shared tokens).
+    One launch, no workspace.  Returns o."""
+    _chk_f16_rows(o, "ip_attention_add.o")
+    _chk_f16_rows(q, "ip_attention_add.q")
+    Cn = heads * d
+    for t, name in ((o, "o"), (q, "q")):
+        if t.shape[0] != B * N or t.shape[1] < Cn:
+            raise RuntimeError(f"ip_attention_add.{name}: expected [{B * N}, >= {Cn}], got {tuple(t.shape)}")
+    for t, name in ((k, "k"), (v, "v")):
+        if t.dtype != F16 or not t.is_cuda or t.dim() != 3 or t.stride(2) != 1 or t.shape[0] != B or t.shape[2] != Cn or t.shape[1] != k.shape[1]:
+            raise RuntimeError(f"ip_attention_add.{name}: expected an fp16 device view [{B}, T, {Cn}] with contiguous channels, got {t.dtype} {t.device} "
+                               f"{tuple(t.shape)} strides {t.stride()}")
+    _launch("af_ip_attention_add", _p(o), _ld(o), _p(q), _ld(q), _p(k), k.stride(1), k.stride(0), _p(v), v.stride(1), v.stride(0),
+            B, N, k.shape[1], heads, d, float(d ** -0.5 if scale is None else scale), float(ip_scale))
+    return o
+
+
 def softmax_rows_bwd(p, dp):
     """ds = p * (dp - rowsum(p * dp)) for fp16 [rows, L] probabilities and their gradient."""
     _chk_f16(p, "softmax_rows_bwd.p")

@@ -482,6 +482,18 @@ int af_vae_attention(const void* q, const void* k, const void* vt, void* o, int 
  * qkv costs 2 (3C + C) bytes per row.
  * AF_E_BADARG (before any launch): NULL pointer, a size outside the above, B*F*HW*ld or B*F*HW*C >= 2^31. */
 int af_temporal_attention(const void* qkv, int ld, void* out, int B, int F, int HW, int heads, int d, float scale, void* stream);
+/* The image-prompt half of IP-Adapter's decoupled cross-attention, added in place to the text attention's output o:
+ *   o[b*N+i, h*d+j] = fp16( float(o[b*N+i, h*d+j]) + ip_scale * sum_t softmax_t(scale * <q[b,i,h,:], k[b,t,h,:]>) * v[b,t,h,j] ),  t over T tokens.
+ * q fp16 [B*N, ldq] (read only), o fp16 [B*N, ldo] (updated in place).  k and v are ROW-MAJOR fp16 token rows: token t of batch item b starts
+ * at k + b*k_bstride + t*ldk (v likewise) and holds its heads*d channels contiguously, so a layer reads its column slice of one stacked
+ * [to_k_ip | to_v_ip] projection of all layers in place.  1 <= T <= 64, d % 8 == 0, 8 <= d <= 160, any N >= 1; row strides are multiples
+ * of 8 and >= heads*d, batch strides multiples of 8 (0 shares one token set), pointers 16-byte aligned, B and heads <= 65535.
+ * One launch, no workspace; every q and o element is touched once with 16-byte accesses, K and V of a (b, h) stay in registers / LDS.
+ * fp32 scores, softmax and accumulation; P is rounded to fp16 once as the MFMA operand; the text and image results are summed in fp32 and
+ * rounded once.  ip_scale == 0 returns AF_OK without a launch.
+ * AF_E_BADARG (before any launch): NULL pointer, a size or stride outside the above, an operand of 2^31 elements or more. */
+int af_ip_attention_add(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, int64_t k_bstride, const void* v, int ldv,
+                        int64_t v_bstride, int B, int N, int T, int heads, int d, float scale, float ip_scale, void* stream);
 /* its backward, ds = p * (dp - rowsum(p * dp)), for the decode-with-grad path of the ArcFace alignment loss (ddpm.py:2511-2535
  * differentiates through decode_first_stage_with_grad, ddpm.py:899-908) */
 int af_softmax_rows_bwd(const void* p, const void* dp, void* ds, int64_t rows, int L, void* stream);
