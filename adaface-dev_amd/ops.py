@@ -1371,9 +1371,33 @@ def im2col3x3(x, stride=1):
 
 
 # ----------------------------------------------------------------------------- ArcFace ResNetFace encoder
+def _chk_face_params(op, device, Cn, scale=None, shift=None, slope=None):
+    """scale / shift: contiguous fp32 [C] on the tensors' device, both or neither; slope: one fp32 value there (nn.PReLU())."""
+    if (scale is None) != (shift is None):
+        raise RuntimeError(f"{op}.{'shift' if shift is None else 'scale'}: scale and shift go together")
+    for name, t, shape in (("scale", scale, (Cn,)), ("shift", shift, (Cn,)), ("slope", slope, (1,))):
+        if t is not None and (t.dtype != torch.float32 or t.device != device or not t.is_contiguous() or tuple(t.shape) != shape):
+            raise RuntimeError(f"{op}.{name}: expected contiguous fp32 {shape} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _chk_f16_like(t, ref, shape, name):
+    """t: a contiguous fp16 tensor of ``shape`` on ``ref``'s device."""
+    _chk_f16(t, name)
+    if tuple(t.shape) != tuple(shape) or t.device != ref.device:
+        raise RuntimeError(f"{name}: expected {tuple(shape)} on {ref.device}, got {tuple(t.shape)} on {t.device}")
+
+
+def _chk_even_nhwc(x, name):
+    _chk_nhwc(x, name)
+    if x.shape[1] % 2 or x.shape[2] % 2:
+        raise RuntimeError(f"{name}: the 2x2 / stride 2 pool needs an even height and width, got {tuple(x.shape)}")
+
+
 def affine_prelu(x, scale=None, shift=None, slope=None):
     """y = prelu(x * scale[c] + shift[c]) over the last (channel) axis; any of the two stages may be absent."""
+    _chk_f16(x, "affine_prelu.x")
     Cn = x.shape[-1]
+    _chk_face_params("affine_prelu", x.device, Cn, scale, shift, slope)
     y = torch.empty_like(x)
     _launch("af_affine_prelu", _p(x), _p(scale), _p(shift), _p(slope), _p(y), x.numel() // Cn, Cn)
     return y
@@ -1629,6 +1653,8 @@ def retina_nms(cand, count, nms_thr, max_det=64):
 
 
 def maxpool2x2(x):
+    """2x2 / stride 2 max over NHWC fp16; the height and width must be even (the kernel rebuilds the source row stride from the output width)."""
+    _chk_even_nhwc(x, "maxpool2x2.x")
     B, H2, W2, Cn = x.shape
     y = torch.empty((B, H2 // 2, W2 // 2, Cn), dtype=F16, device=x.device)
     _launch("af_maxpool2x2", _p(x), _p(y), B, H2 // 2, W2 // 2, Cn)
@@ -1636,6 +1662,9 @@ def maxpool2x2(x):
 
 
 def global_avgpool(x):
+    _chk_f16(x, "global_avgpool.x")
+    if x.dim() != 4 or x.numel() == 0:
+        raise RuntimeError(f"global_avgpool.x: expected a non-empty NHWC tensor, got {tuple(x.shape)}")
     B, H, W, Cn = x.shape
     out = torch.empty((B, Cn), dtype=F16, device=x.device)
     _launch("af_global_avgpool", _p(x), _p(out), B, H * W, Cn)
@@ -1643,7 +1672,14 @@ def global_avgpool(x):
 
 
 def se_residual_prelu(x, se_logits, residual, slope):
+    _chk_nhwc(x, "se_residual_prelu.x")
     B, H, W, Cn = x.shape
+    _chk_f16_like(residual, x, x.shape, "se_residual_prelu.residual")
+    if se_logits is not None:
+        _chk_f16_like(se_logits, x, (B, Cn), "se_residual_prelu.se_logits")
+    if slope is None:
+        raise RuntimeError("se_residual_prelu.slope: the block's PReLU slope is required")
+    _chk_face_params("se_residual_prelu", x.device, Cn, slope=slope)
     y = torch.empty_like(x)
     _launch("af_se_residual_prelu", _p(x), _p(se_logits), _p(residual), _p(slope), _p(y), B, H * W, Cn)
     return y
@@ -1653,22 +1689,44 @@ def affine_prelu_bwd(dy, x=None, scale=None, shift=None, slope=None):
     """Input gradient of ``affine_prelu``; x (the forward input) is only read when there is a PReLU."""
     _chk_f16(dy, "affine_prelu_bwd.dy")
     Cn = dy.shape[-1]
+    if x is not None:
+        _chk_f16_like(x, dy, dy.shape, "affine_prelu_bwd.x")
+    elif slope is not None:
+        raise RuntimeError("affine_prelu_bwd.x: the PReLU gradient needs the forward input x")
+    _chk_face_params("affine_prelu_bwd", dy.device, Cn, scale, shift, slope)
     dx = torch.empty_like(dy)
     _launch("af_affine_prelu_bwd", _p(x), _p(scale), _p(shift), _p(slope), _p(dy), _p(dx), dy.numel() // Cn, Cn)
     return dx
 
 
 def maxpool2x2_bwd(x, dy):
-    _chk_f16(dy, "maxpool2x2_bwd.dy")
+    """dy routed to the first maximum of each 2x2 window of x (torch's rule); every element of dx is written."""
+    _chk_even_nhwc(x, "maxpool2x2_bwd.x")
     B, H2, W2, Cn = x.shape
+    _chk_f16_like(dy, x, (B, H2 // 2, W2 // 2, Cn), "maxpool2x2_bwd.dy")
     dx = torch.empty_like(x)
     _launch("af_maxpool2x2_bwd", _p(x), _p(dy), _p(dx), B, H2 // 2, W2 // 2, Cn)
     return dx
 
 
+def _chk_se_operands(op, x, se_logits, residual, slope, dy):
+    _chk_f16(x, f"{op}.x")
+    if x.dim() != 4 or x.numel() == 0:
+        raise RuntimeError(f"{op}.x: expected a non-empty NHWC tensor, got {tuple(x.shape)}")
+    _chk_f16_like(residual, x, x.shape, f"{op}.residual")
+    _chk_f16_like(dy, x, x.shape, f"{op}.dy")
+    if se_logits is not None:
+        _chk_f16_like(se_logits, x, (x.shape[0], x.shape[3]), f"{op}.se_logits")
+    if slope is None:
+        raise RuntimeError(f"{op}.slope: the block's PReLU slope is required")
+    _chk_face_params(op, x.device, x.shape[3], slope=slope)
+
+
 def se_gate_grad(x, se_logits, residual, slope, dy):
     """-> fp16 [B, C]: gradient of the SE logits divided by H*W (see include/adaface_hip.h)."""
-    _chk_f16(dy, "se_gate_grad.dy")
+    if se_logits is None:
+        raise RuntimeError("se_gate_grad.se_logits: the gate logits are required")
+    _chk_se_operands("se_gate_grad", x, se_logits, residual, slope, dy)
     B, H, W, Cn = x.shape
     dgl = torch.empty((B, Cn), dtype=F16, device=x.device)
     _launch("af_se_gate_grad", _p(x), _p(se_logits), _p(residual), _p(slope), _p(dy), _p(dgl), B, H * W, Cn)
@@ -1677,8 +1735,10 @@ def se_gate_grad(x, se_logits, residual, slope, dy):
 
 def se_residual_prelu_bwd(x, se_logits, residual, slope, dy, dpool=None):
     """-> (dx, dresidual) of ``se_residual_prelu``; dpool [B, C] is the squeeze branch's gradient (1/HW included)."""
-    _chk_f16(dy, "se_residual_prelu_bwd.dy")
+    _chk_se_operands("se_residual_prelu_bwd", x, se_logits, residual, slope, dy)
     B, H, W, Cn = x.shape
+    if dpool is not None:
+        _chk_f16_like(dpool, x, (B, Cn), "se_residual_prelu_bwd.dpool")
     dx, dres = torch.empty_like(x), torch.empty_like(x)
     _launch("af_se_residual_prelu_bwd", _p(x), _p(se_logits), _p(residual), _p(slope), _p(dy), _p(dpool), _p(dx), _p(dres), B, H * W, Cn)
     return dx, dres
