@@ -90,6 +90,16 @@ U-Net during the sampling call only, and the sampler's per-step callback switche
 into the U-Net's weights while the adapter is loaded (``unload_ip_adapter`` restores them).  Without these arguments every path is the call
 as it was.
 
+``forward(..., region_masks=[m1, m2], region_prompts=[p1, p2] | region_prompt_embeds=[e1, e2], region_base_weight=0.2)`` (INTEGRATION.md
+"Regional prompts / several subjects") composes several prompts -- and, through ``region_prompt_embeds``, several subjects -- in one picture
+on all three pipelines, under all three samplers, with ``control_image`` and with an IP-Adapter: every cross-attention layer attends to the
+base prompt and to each region's prompt and blends the results per token under the masks (PIL "L" images, uint8 arrays or tensors of the
+image's size, white = the region), area-averaged onto the layer's token grid: ``w_r = (1 - beta) m_r / max(1, s)``, the base prompt keeps
+``beta + (1 - beta)(1 - min(1, s))`` (``ops.region_weights``, ``ops.region_attention``: one launch per layer, a region's K / V are not read
+where it has no weight).  The unconditional half runs the negative prompt alone.  The regions sit on the U-Net during the sampling call only
+(``UNetModel.set_regions``).  Not built: regions with ``num_frames``, ``hires_size`` or ``crop_padding``.  Without these arguments every
+path is the call as it was.
+
 ``forward(photo, ..., mask_image="face", crop_padding=0.5)`` (``inpaint`` only; INTEGRATION.md "Repainting faces in a photo") repaints
 the faces of ONE photo of any size (a PIL image, a path or a uint8 array) and hands back the same photo: ``face_detector`` (any callable
 with ``FaceIDExtractor``'s detector contract, e.g. a ``RetinaFaceDetector``; by default the ``face_id_extractor``'s) finds the faces,
@@ -444,13 +454,14 @@ class AdaFaceWrapper(nn.Module):
             raise ValueError(f"control images must be exactly 8 x the latent size, {8 * latent_hw[1]} x {8 * latent_hw[0]} pixels, got "
                              f"{images.shape[2]} x {images.shape[1]} (nothing is resized)")
 
-    def _sample_controlled(self, control, n_steps, call, ip=None):
+    def _sample_controlled(self, control, n_steps, call, ip=None, regions=None):
         """``call(**kw)`` runs one of the sampler's loops.  With ``control`` = (images uint8, scale, start, end) the ControlNet is on the
         U-Net around that call only: the hints are encoded once, and the sampler's per-step callback switches the control off and on by the
         guidance window (active at step i of n iff i / n >= start and (i + 1) / n <= end).  With ``ip`` = (cond tokens, uncond tokens, scale,
         start, end) the IP-Adapter is on the U-Net in the same way, under its own window.  Without either this is ``call()``: the sampler is
-        called exactly as before."""
-        if control is None and ip is None:
+        called exactly as before.  With ``regions`` = (contexts, uncond context, level weights) the regional prompts are set on the U-Net around
+        the call too (UNetModel.set_regions; no window)."""
+        if control is None and ip is None and regions is None:
             return call()
         from ..ldm.modules.diffusionmodules.controlnet import guidance_window_active
         unet = self.ldm.model.diffusion_model
@@ -462,16 +473,86 @@ class AdaFaceWrapper(nn.Module):
                 unet.set_ip_adapter_active(i < n_steps and guidance_window_active(i, n_steps, ip[3], ip[4]))
 
         try:
+            if regions is not None:
+                unet.set_regions(*regions)
             if control is not None:
                 cn = self.controlnet.to(self.device)
                 unet.set_control(cn, cn.hint_features(control[0].to(self.device)), control[1])
             if ip is not None:
                 unet.set_ip_adapter(self.ip_adapter, ip[0], ip[1], ip[2])
+            if control is None and ip is None:
+                return call()
             switch(0)
             return call(callback=lambda i: switch(i + 1))                # the callback runs behind step i
         finally:
             unet.set_control(None)
             unet.set_ip_adapter(None)
+            unet.set_regions(None)
+
+    # ------------------------------------------------------------------ regional prompts (INTEGRATION.md "Regional prompts / several subjects")
+    def _check_regions(self, masks, prompts, embeds, beta, num_frames, hires_size, crop_padding):
+        """The refusals of forward(region_masks=...) that do not need the image size, all before any GPU work.  Returns the masks as one uint8
+        array [R - 1, H, W] (white = the region)."""
+        if masks is None:
+            raise ValueError("region_prompts / region_prompt_embeds are given without region_masks")
+        if (prompts is None) == (embeds is None):
+            raise ValueError("regions need exactly one of region_prompts (strings) and region_prompt_embeds (encode_prompt results)")
+        for name, v in (("num_frames", num_frames), ("hires_size", hires_size), ("crop_padding", crop_padding)):
+            if v is not None:
+                raise ValueError(f"regional prompts are not built with {name}")
+        if torch.is_tensor(masks) or isinstance(masks, np.ndarray):
+            masks = list(masks) if masks.ndim == 3 else [masks]
+        if not isinstance(masks, (list, tuple)) or not masks:
+            raise ValueError("region_masks must be a list of PIL 'L' images, uint8 arrays or tensors [H, W]")
+        given = prompts if prompts is not None else embeds
+        if not isinstance(given, (list, tuple)) or len(given) != len(masks):
+            raise ValueError(f"{len(masks)} region masks but {len(given) if isinstance(given, (list, tuple)) else type(given).__name__} region prompts: "
+                             "one prompt per mask")
+        if len(masks) > ops.REGION_MAX - 1:
+            raise ValueError(f"at most {ops.REGION_MAX - 1} regions (beside the base prompt), got {len(masks)}")
+        if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0 <= beta <= 1:
+            raise ValueError(f"region_base_weight must be in [0, 1], got {beta!r}")
+        if prompts is not None and not all(isinstance(t, str) for t in prompts):
+            raise ValueError("region_prompts must be strings")
+        if embeds is not None and not all(isinstance(e, (list, tuple)) and len(e) in (2, 4) and torch.is_tensor(e[0]) and e[0].dim() == 3 for e in embeds):
+            raise ValueError("region_prompt_embeds must hold one encode_prompt result (a 2- or 4-tuple of embeddings) per region")
+        out = []
+        for m in masks:
+            if torch.is_tensor(m):
+                m = m.detach().cpu().numpy()
+            elif not isinstance(m, np.ndarray):
+                m = np.asarray(m.convert("L")) if hasattr(m, "convert") else np.asarray(m)
+            if m.dtype == np.bool_:
+                m = m.astype(np.uint8) * 255
+            if m.ndim != 2 or m.dtype != np.uint8:
+                raise ValueError(f"a region mask must be a PIL 'L' image or uint8 [H, W] (255 = the region), got {m.dtype} {m.shape}")
+            if out and m.shape != out[0].shape:
+                raise ValueError(f"the region masks differ in size: {out[0].shape} and {m.shape}")
+            out.append(m)
+        return np.ascontiguousarray(np.stack(out, 0))
+
+    @staticmethod
+    def _check_region_size(masks_u8, hw):
+        if hw[0] % 64 or hw[1] % 64:
+            raise ValueError(f"regional prompts need an image whose sides are multiples of 64 pixels, got {hw[1]} x {hw[0]}")
+        if tuple(masks_u8.shape[1:]) != tuple(hw):
+            raise ValueError(f"the region masks must be the image's size, {hw[1]} x {hw[0]} pixels, got {masks_u8.shape[2]} x {masks_u8.shape[1]} "
+                             "(nothing is resized)")
+
+    def _region_state(self, masks_u8, prompts, embeds, beta, pe, ne, kw):
+        """(contexts fp16 [rows, R, L, C], uncond context fp16 [rows, L, C], the levels' weights) for UNetModel.set_regions: set 0 is the base
+        prompt ``pe`` [rows, L, C], the regions' prompts are encoded with the subject currently set."""
+        if prompts is not None:
+            embeds = [self.encode_prompt(t, None, device=self.device, **kw) for t in prompts]
+        rows = pe.shape[0]
+        sets = [pe] + [e[0].to(self.device).expand(rows, -1, -1) if e[0].shape[0] == 1 else e[0].to(self.device) for e in embeds]
+        for t in sets[1:]:
+            if tuple(t.shape) != tuple(pe.shape):
+                raise ValueError(f"a region's prompt embeddings are {tuple(t.shape)}, the base prompt's {tuple(pe.shape)}")
+        contexts = torch.stack([t.to(torch.float16) for t in sets], 1).contiguous()
+        uncond = (pe if ne is None else ne).to(torch.float16).contiguous()
+        _, levels = ops.region_weights(torch.from_numpy(masks_u8).to(self.device), float(beta))
+        return contexts, uncond, levels
 
     # ------------------------------------------------------------------ IP-Adapter (adaface/ip_adapter.py; INTEGRATION.md "IP-Adapter")
     def load_ip_adapter(self, path_or_obj, image_encoder=None, lora_scale=1.0):
@@ -793,7 +874,8 @@ class AdaFaceWrapper(nn.Module):
                 hires_steps=None, hires_upscaler="bilinear", crop_padding=None, face_index=None, face_mask_expand=1.3,
                 face_mask_feather=0.25, work_size=None, num_frames=None, upscale=False, restore_faces=False, control_image=None,
                 control_scale=1.0, control_guidance_start=0.0, control_guidance_end=1.0, ip_adapter_image=None, ip_adapter_face_id=None,
-                ip_adapter_scale=1.0, ip_guidance_start=0.0, ip_guidance_end=1.0):
+                ip_adapter_scale=1.0, ip_guidance_start=0.0, ip_guidance_end=1.0, region_masks=None, region_prompts=None,
+                region_prompt_embeds=None, region_base_weight=0.2):
         if self.ldm is None:
             raise RuntimeError("pipeline_name=None builds the face encoder only")
         if upscale:
@@ -812,6 +894,12 @@ class AdaFaceWrapper(nn.Module):
         ip_in = None
         if ip_adapter_image is not None or ip_adapter_face_id is not None:
             ip_in = self._check_ip(ip_adapter_image, ip_adapter_face_id, ip_adapter_scale, ip_guidance_start, ip_guidance_end, out_image_count)
+        region_masks_u8 = None
+        if region_masks is not None or region_prompts is not None or region_prompt_embeds is not None:
+            region_masks_u8 = self._check_regions(region_masks, region_prompts, region_prompt_embeds, region_base_weight, num_frames, hires_size,
+                                                  crop_padding)
+            if repaint is not None:
+                raise ValueError("regional prompts are not built with repainting a photo (mask_image='face' or crop_padding)")
         if hires_size is not None:
             hires_hw, hires_steps = self._check_hires(hires_size, hires_strength, hires_steps, hires_upscaler)
         if upscale and self.pipeline_name == "text2img":
@@ -844,6 +932,8 @@ class AdaFaceWrapper(nn.Module):
             self._sampler().img2img_steps(self.num_inference_steps, ref_img_strength)    # refuse a bad strength before any work
             if control is not None:
                 self._check_control_size(control[0], (images_u8.shape[1] // 8, images_u8.shape[2] // 8))
+            if region_masks_u8 is not None:
+                self._check_region_size(region_masks_u8, tuple(images_u8.shape[1:3]))
         elif self.vae is not None and torch.is_tensor(noise) and noise.dim() == 4 and max(noise.shape[2:]) * 8 > MAX_IMAGE_SIDE:
             raise ValueError(f"text2img latents may be at most {MAX_IMAGE_SIDE // 8} on a side ({MAX_IMAGE_SIDE} pixels, the VAE's limit), got "
                              f"noise of shape {tuple(noise.shape)}")
@@ -851,6 +941,10 @@ class AdaFaceWrapper(nn.Module):
             if not torch.is_tensor(noise) or noise.dim() != 4:
                 raise ValueError("control_image needs noise [rows, 4, h, w] to take the latent size from")
             self._check_control_size(control[0], tuple(noise.shape[2:]))
+        if region_masks_u8 is not None and self.pipeline_name == "text2img":
+            if not torch.is_tensor(noise) or noise.dim() != 4:
+                raise ValueError("region_masks need noise [rows, 4, h, w] to take the image size from")
+            self._check_region_size(region_masks_u8, (noise.shape[2] * 8, noise.shape[3] * 8))
         if prompt_embeds is None:
             pe, ne, _, _ = self.encode_prompt(prompt, negative_prompt, placeholder_tokens_pos=placeholder_tokens_pos,
                                               ablate_prompt_only_placeholders=ablate_prompt_only_placeholders,
@@ -871,13 +965,18 @@ class AdaFaceWrapper(nn.Module):
         ip = None
         if ip_in is not None:
             ip = self._ip_tokens(ip_in[0], ip_in[1], out_image_count) + (float(ip_adapter_scale), ip_guidance_start, ip_guidance_end)
+        regions = None
+        if region_masks_u8 is not None:
+            regions = self._region_state(region_masks_u8, region_prompts, region_prompt_embeds, region_base_weight, pe.to(self.device),
+                                         None if ne is None else ne.to(self.device),
+                                         dict(placeholder_tokens_pos=placeholder_tokens_pos, repeat_prompt_for_each_encoder=repeat_prompt_for_each_encoder))
         if self.pipeline_name == "img2img":
             n_run, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
             x_t = self.ldm.img2img_latents(images_u8.to(self.device), out_image_count, t_first, generator=generator,
                                            first_stage_model=self.vae)
             latents, _ = self._sample_controlled(control, n_run, lambda **cb: sampler.sample_img2img(
                 self.num_inference_steps, ref_img_strength, out_image_count, x_t, cond, guidance_scale=guidance_scale,
-                unconditional_conditioning=uncond, generator=generator, **cb), ip)
+                unconditional_conditioning=uncond, generator=generator, **cb), ip, regions)
             return self._to_pil(latents, upscale, restore_faces)
         if inpaint:
             n_run, t_first = sampler.img2img_steps(self.num_inference_steps, ref_img_strength)
@@ -892,7 +991,7 @@ class AdaFaceWrapper(nn.Module):
                                                          first_stage_model=self.vae, from_noise=ref_img_strength == 1)
             latents, _ = self._sample_controlled(control, n_run, lambda **cb: sampler.sample_inpaint(
                 self.num_inference_steps, ref_img_strength, out_image_count, x_start, z, n_fwd, masks.to(self.device), cond,
-                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb), ip)
+                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb), ip, regions)
             if repaint is not None:
                 return self._paste_back(latents, photo, alpha, repaint["rect"], upscale, restore_faces)
             return self._to_pil(latents, upscale, restore_faces)
@@ -905,7 +1004,7 @@ class AdaFaceWrapper(nn.Module):
             n_run = len(sampler.timesteps(self.num_inference_steps)) if control is not None or ip is not None else None
             latents, _ = self._sample_controlled(control, n_run, lambda **cb: sampler.sample(
                 self.num_inference_steps, out_image_count, tuple(noise.shape[1:]), conditioning=cond, x_T=noise, verbose=False,
-                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb), ip)
+                guidance_scale=guidance_scale, unconditional_conditioning=uncond, generator=generator, **cb), ip, regions)
         finally:
             if num_frames is not None:
                 unet.set_motion(None)

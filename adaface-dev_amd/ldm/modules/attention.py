@@ -56,12 +56,13 @@ def ln_fold(C, M=None) -> bool:
     return bool(FOLD_LAYERNORM and C % 64 == 0 and (M is None or M >= LN_FOLD_MIN_ROWS))
 
 
-def xattn_route(C, B, N, L, heads, inner_dim, folded, capture=False, masked=False, chain=False, ip=False) -> str:
+def xattn_route(C, B, N, L, heads, inner_dim, folded, capture=False, masked=False, chain=False, ip=False, regions=False) -> str:
     """How a cross-attention layer over L context tokens runs: "split" (q projection, attention core, to_out), "fused" (ONE launch: af_xattn_fused) or,
     where the caller offers the self-attention's to_out in front (``chain``), "chain" (af_xattn_chain).  ``folded``: its LayerNorm is folded into to_q.
     ``ip``: the layer carries IP-Adapter image tokens (CrossAttention._ip_pre): their softmax is added to the attention core's output, which the
-    one-launch forms never materialise, so such a layer runs "split"."""
-    if not (FUSE_XATTN and folded and L is not None and L <= 80 and heads == 8 and inner_dim == C and not capture and not masked and not ip):
+    one-launch forms never materialise, so such a layer runs "split".  ``regions``: the layer attends to several context sets under region weights
+    (CrossAttention._region_pre, af_region_attention), a core the one-launch forms do not hold: "split" as well."""
+    if not (FUSE_XATTN and folded and L is not None and L <= 80 and heads == 8 and inner_dim == C and not capture and not masked and not ip and not regions):
         return "split"
     if C == 320 and N % 128 == 0 and B * N >= XATTN_FUSE_MIN_TOKENS:        # 128-token workgroups: once they cover enough of the chip
         return "chain" if chain and CHAIN_XATTN else "fused"
@@ -92,13 +93,13 @@ class BlockPlan(NamedTuple):
         return self.ff in ("chain", "fold")
 
 
-def block_plan(C, B, N, L, heads, inner_dim, capture1=False, capture2=False, want_proj_out=False, can_fold_proj_out=False, ip=False) -> BlockPlan:
+def block_plan(C, B, N, L, heads, inner_dim, capture1=False, capture2=False, want_proj_out=False, can_fold_proj_out=False, ip=False, regions=False) -> BlockPlan:
     """The plan of one block on [B * N, C] rows with L context tokens (None: attn2 is a self-attention).  capture1 / capture2: attn1 / attn2 save their
     cross-attention variables (a capturing attn1 needs its own output: no chain); want_proj_out: the caller is the SpatialTransformer's last block and
     offers its proj_out; can_fold_proj_out: it has the folded pack (ops.pack_ff_proj_out) for that; ip: attn2 carries IP-Adapter image tokens (xattn_route),
-    the feed-forward plan does not depend on it."""
+    regions: attn2 runs regional prompts (xattn_route); the feed-forward plan depends on neither."""
     fold12, fold3 = ln_fold(C, B * N), ln_fold(C)
-    return BlockPlan(not fold12, not fold3, xattn_route(C, B, N, L, heads, inner_dim, fold12, capture2, chain=not capture1, ip=ip),
+    return BlockPlan(not fold12, not fold3, xattn_route(C, B, N, L, heads, inner_dim, fold12, capture2, chain=not capture1, ip=ip, regions=regions),
                      ff_route(C, B * N, fold3, want_proj_out, can_fold_proj_out))
 
 
@@ -225,6 +226,7 @@ class CrossAttention(nn.Module):
         self.cached_activations = None
         self._kv_pre = None
         self._ip_pre = None      # (k_ip [B, T, inner_dim], v_ip [B, T, inner_dim], ip_scale) while UNetModel.hip runs with an IP-Adapter set: views into its stacked projection
+        self._region_pre = None  # (k, vt, ldk, vt_batch_stride, {N: w [B*R, N] fp32}, R) while UNetModel.hip runs with regions set: this layer's slices of the stacked projection of all context sets
         self._qkv_cache = _PackCache()
         self._kv_cache = _PackCache()
 
@@ -279,19 +281,34 @@ class CrossAttention(nn.Module):
             k = q[:, Ci:]
         else:
             L = context.shape[1]
+            if self.save_cross_attn_vars:
+                self._refuse_regions("the capture path (save_cross_attn_vars)")
             k, vt, ldk = self._kv(context, B)
-            ip = self._ip_pre
+            ip, rg = self._ip_pre, self._region_pre
             if self.save_cross_attn_vars:
                 self._refuse_ip("the capture path (save_cross_attn_vars)")
-            if (route or xattn_route(x2d.shape[1], B, N, L, h, Ci, ln is not None, self.save_cross_attn_vars, keybias is not None, ip=ip is not None)) == "fused":
+            if (route or xattn_route(x2d.shape[1], B, N, L, h, Ci, ln is not None, self.save_cross_attn_vars, keybias is not None, ip=ip is not None,
+                                     regions=rg is not None)) == "fused":
                 if ip is not None:
                     raise RuntimeError("CrossAttention.hip: a layer with IP-Adapter image tokens cannot run the one-launch route (xattn_route(ip=True) is \"split\")")
+                if rg is not None:
+                    raise RuntimeError("CrossAttention.hip: a layer with regions placed cannot run the one-launch route (xattn_route(regions=True) is \"split\")")
                 # the 64 x 64 level: q projection (norm2 folded in), the 77-key core, to_out and the residual as ONE launch over 128-token tiles
                 # that stay in LDS (af_xattn_fused, tiled form)
                 return ops.xattn_fused(x2d, self._packed_q_ln(ln), k, vt, self.to_out[0].packed(), B=B, N=N, L=L, heads=h, scale=self.scale,
                                        ldk=ldk, residual=residual)
             q = self.to_q.hip(x2d) if ln is None else ops.gemm(x2d, self._packed_q_ln(ln))
-            o = ops.attention(q, k, vt, B=B, Nq=N, L=L, heads=h, d=d, ldq=Ci, ldk=ldk, keybias=keybias, scale=self.scale)
+            if rg is not None:
+                # regional prompts: one launch attends to every context set the tile's region weights reach and blends them in fp32 (af_region_attention);
+                # k / vt above (the base context's, still what a ControlNet beside this U-Net reads) are not used by this layer
+                if keybias is not None:
+                    raise NotImplementedError("regional prompts are not built with a key mask (img_mask)")
+                rk, rvt, rldk, _, rw, R = rg                 # (rvt is a row slice of the stacked V^T: its strides carry ldv and the batch stride)
+                if N not in rw:
+                    raise ValueError(f"the region weights hold the levels of {sorted(rw)} tokens, this layer has {N}: the latents are not the size the regions were set for")
+                o = ops.region_attention(q, rk, rvt, rw[N], B=B, R=R, N=N, L=L, heads=h, d=d, ldk=rldk, scale=self.scale)
+            else:
+                o = ops.attention(q, k, vt, B=B, Nq=N, L=L, heads=h, d=d, ldq=Ci, ldk=ldk, keybias=keybias, scale=self.scale)
             if ip is not None:
                 # decoupled cross-attention: the softmax over the image tokens, added to the text result in fp32 in place (af_ip_attention_add)
                 ops.ip_attention_add(o, q, ip[0], ip[1], B=B, N=N, heads=h, d=d, ip_scale=ip[2], scale=self.scale)
@@ -320,6 +337,10 @@ class CrossAttention(nn.Module):
         if self._ip_pre is not None:
             raise NotImplementedError(f"{what} is not built with an IP-Adapter: unset it (set_ip_adapter(None)) first")
 
+    def _refuse_regions(self, what):
+        if self._region_pre is not None:
+            raise NotImplementedError(f"{what} is not built with regional prompts: unset them (set_regions(None)) first")
+
     # ---- training mode: row-major q|k|v kept for the flash backward
     def _packed_qkv_bwd(self):
         ws = (self.to_q.weight, self.to_k.weight, self.to_v.weight)
@@ -338,6 +359,7 @@ class CrossAttention(nn.Module):
         backward is unchanged: it differentiates the projection w.r.t. LN's output and the caller's LayerNorm backward does the rest)."""
         Ci, h, d = self.inner_dim, self.heads, self.dim_head
         self._refuse_ip("hip_train")
+        self._refuse_regions("hip_train")
         if context is None:
             qkv = ops.gemm(x2d, self._packed_qkv() if ln is None else self._packed_qkv_ln(ln))       # [M, 3C] row-major
             vt = ops.transpose_tokens(qkv[:, 2 * Ci:], B, N, Ci, 3 * Ci)
@@ -356,6 +378,7 @@ class CrossAttention(nn.Module):
     def hip_bwd(self, saved, dy, dctx=None):
         """dy [M, C] -> (dx [M, C], dctx [B*L, Cc] accumulated) -- activation gradients only."""
         Ci, h, d = self.inner_dim, self.heads, self.dim_head
+        self._refuse_regions("hip_bwd")
         do = self.to_out[0].hip_dgrad(dy)
         if saved[0] == "self":
             _, qkv, o, lse, keybias, B, N, L = saved
@@ -396,7 +419,8 @@ class BasicTransformerBlock(nn.Module):
     def plan(self, C, B, N, context, want_proj_out=False, can_fold_proj_out=False) -> BlockPlan:
         """block_plan of this block's layers on [B * N, C] rows."""
         return block_plan(C, B, N, None if context is None else context.shape[1], self.attn2.heads, self.attn2.inner_dim, self.attn1.save_cross_attn_vars,
-                          self.attn2.save_cross_attn_vars, want_proj_out, can_fold_proj_out, ip=self.attn2._ip_pre is not None)
+                          self.attn2.save_cross_attn_vars, want_proj_out, can_fold_proj_out, ip=self.attn2._ip_pre is not None,
+                          regions=self.attn2._region_pre is not None)
 
     def hip(self, x2d, B, N, context=None, keybias=None, plan=None, pw_out=None, x_in=None, gn_cpg=0):
         """attention.py:242-252 with the three residual adds fused into GEMM epilogues, launched as ``plan`` says (default: self.plan(...), no proj_out).
@@ -408,6 +432,8 @@ class BasicTransformerBlock(nn.Module):
         ln1, ln2, ln3 = (None if p.ln12 else self.norm1), (None if p.ln12 else self.norm2), (None if p.ln3 else self.norm3)
         if p.xattn != "split" and a2._ip_pre is not None:
             raise RuntimeError(f"BasicTransformerBlock.hip: the plan runs attn2 as {p.xattn!r}, which cannot add IP-Adapter image tokens (block_plan(ip=True))")
+        if p.xattn != "split" and a2._region_pre is not None:
+            raise RuntimeError(f"BasicTransformerBlock.hip: the plan runs attn2 as {p.xattn!r}, which cannot run regional prompts (block_plan(regions=True))")
         if p.xattn == "chain":
             # the 64 x 64 level: attn1's to_out + residual run as phase 0 of the one-launch cross-attention block (af_xattn_chain)
             o, pw_o1 = a1.self_core(x2d, B, N, keybias, ln1)[0], a1.to_out[0].packed()

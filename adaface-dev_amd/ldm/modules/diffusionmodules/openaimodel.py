@@ -293,6 +293,15 @@ class ResBlock(TimestepBlock):
         return from_nhwc_f16(self.hip(to_nhwc_f16(x), emb), x.dtype)
 
 
+def _kv_all_pack(net, layers):
+    """The stacked [all to_k | all to_v] weights of ``net``'s cross-attention ``layers``, packed once per weight version (a module-level function:
+    ControlNet borrows ``UNetModel._project_context_all``, which calls it)."""
+    ws = [m.to_k.weight for m in layers] + [m.to_v.weight for m in layers]
+    if not hasattr(net, "_kv_all_cache"):
+        net._kv_all_cache = _PackCache()
+    return net._kv_all_cache.get(ws, lambda: ops.pack_matrix(torch.cat([w.detach() for w in ws], 0), None, ws[0].device))
+
+
 class UNetModel(nn.Module):
     """The SD-1.5 U-Net with the reference's constructor signature (openaimodel.py:444-469).
     Only the options SD-1.5 uses are implemented; the others raise at construction."""
@@ -391,6 +400,7 @@ class UNetModel(nn.Module):
         self._assign_emb_slices()
         self.__dict__["_control"] = None         # set_control's state ({"net", "hint", "scale", "expanded", "active"}) while it holds a ControlNet; not a submodule either
         self.__dict__["_ip"] = None              # set_ip_adapter's state ({"adapter", "rows", "T", "kv", "scale", "active"}) while it holds an IP-Adapter; not a submodule
+        self.__dict__["_regions"] = None         # set_regions' state ({"rows", "R", "L", "k", "vt", "w"}) while regional prompts are set; not a submodule
         self.__dict__["_motion"] = None          # (MotionModule, num_frames) while set_motion holds one; not a submodule: the state dict stays SD-1.5's
 
     # ------------------------------------------------------------------ reference flag plumbing
@@ -485,6 +495,7 @@ class UNetModel(nn.Module):
         if motion is None:
             self.__dict__["_motion"] = None
             return
+        self._refuse_regions("set_motion (video)")
         F = int(num_frames)
         if not 1 <= F <= motion.max_len:
             raise ValueError(f"set_motion: num_frames must be in 1 .. {motion.max_len} (the module's position table), got {num_frames}")
@@ -613,6 +624,89 @@ class UNetModel(nn.Module):
             off += c
         return layers
 
+    # ------------------------------------------------------------------ regional prompts (several subjects)
+    def set_regions(self, contexts, uncond_context=None, weights=None):
+        """Run ``hip`` with regional prompts: every cross-attention layer attends to R context sets per batch row -- set 0 the base prompt, sets
+        1 .. R-1 the regions -- and blends the results per token under the region weights (af_region_attention, one launch per layer).
+        ``contexts``: fp16 [rows, R, L, context_dim]; ``uncond_context``: fp16 [rows, L, context_dim]; ``weights``: the levels' fp32 device
+        tensors [R, N_l] (``ops.region_weights``), one per token count a cross-attention layer of this U-Net will see.  All layers' K | V^T of all
+        sets are projected HERE, once, by ONE GEMM over the stacked [all to_k | all to_v] weights with the sets as batch items; a step adds no
+        projection GEMM.  A batch of ``rows`` runs cond, a batch of 2 x rows cond then uncond (the samplers' order); anything else is a ValueError.
+        The uncond rows run their context under w = (1, 0, ..., 0): their sets 1 .. R-1 are never read and are not projected.  ``hip`` is still
+        given the base context (cond, uncond), which a ControlNet set beside this U-Net reads.  ``None`` restores the plain walk exactly, the
+        one-launch routes included."""
+        if contexts is None:
+            self.__dict__["_regions"] = None
+            return
+        self._refuse_motion("set_regions")
+        layers = self._cross_attn_layers()
+        if not layers:
+            raise ValueError("set_regions: this U-Net has no cross-attention layer")
+        cc = layers[0].to_k.in_features
+        c = contexts
+        if (not torch.is_tensor(c) or c.dtype != F16 or c.dim() != 4 or c.shape[0] < 1 or c.shape[3] != cc or not 1 <= c.shape[1] <= ops.REGION_MAX
+                or not 1 <= c.shape[2] <= ops.REGION_MAX_TOKENS):
+            raise ValueError(f"set_regions: contexts must be fp16 [rows, 1 <= R <= {ops.REGION_MAX}, 1 <= L <= {ops.REGION_MAX_TOKENS}, {cc}], got "
+                             f"{(c.dtype, tuple(c.shape)) if torch.is_tensor(c) else type(c).__name__}")
+        rows, R, L, _ = c.shape
+        u = uncond_context
+        if not torch.is_tensor(u) or u.dtype != F16 or tuple(u.shape) != (rows, L, cc):
+            raise ValueError(f"set_regions: uncond_context must be fp16 [{rows}, {L}, {cc}], got "
+                             f"{(u.dtype, tuple(u.shape)) if torch.is_tensor(u) else type(u).__name__}")
+        if not isinstance(weights, (list, tuple)) or not weights:
+            raise ValueError("set_regions: weights must be the levels' fp32 tensors [R, N_l] (ops.region_weights)")
+        for t in weights:
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != R or t.shape[1] < 1:
+                raise ValueError(f"set_regions: every level's weights must be fp32 [{R}, N_l], got "
+                                 f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+        if len({t.shape[1] for t in weights}) != len(weights):
+            raise ValueError(f"set_regions: two levels of weights have the same token count ({[t.shape[1] for t in weights]})")
+        dev = c.device
+        pack = _kv_all_pack(self, layers)
+        sc = pack.N // 2
+        # the projected items: rows x R cond sets, then the rows' uncond contexts; placed as batch item b R + r of a [2 rows R] stack whose
+        # uncond sets 1 .. R-1 stay zero (weight 0: never read)
+        src = torch.cat([c.reshape(rows * R, L, cc), u.to(dev)], 0).reshape((rows * R + rows) * L, cc).contiguous()
+        k_p, vt_p = ops.gemm(src, pack, rows_per_batch=L, split_col=sc)
+        k = torch.zeros((2 * rows * R * L, sc), dtype=F16, device=dev)
+        vt = torch.zeros((2 * rows * R,) + tuple(vt_p.shape[1:]), dtype=F16, device=dev)
+        k[:rows * R * L] = k_p[:rows * R * L]
+        vt[:rows * R] = vt_p[:rows * R]
+        k[rows * R * L:].reshape(rows, R, L, sc)[:, 0] = k_p[rows * R * L:].reshape(rows, L, sc)
+        vt[rows * R:].reshape((rows, R) + tuple(vt_p.shape[1:]))[:, 0] = vt_p[rows * R:]
+        w = {}
+        for t in weights:
+            full = torch.zeros((2 * rows, R, t.shape[1]), dtype=torch.float32, device=dev)
+            full[:rows] = t.to(dev)[None]
+            full[rows:, 0] = 1.0
+            w[t.shape[1]] = full.reshape(2 * rows * R, t.shape[1])
+        self.__dict__["_regions"] = {"rows": rows, "R": R, "L": L, "k": k, "vt": vt, "w": w}
+
+    def _refuse_regions(self, what):
+        if self._regions is not None:
+            raise NotImplementedError(f"{what} is not built with regional prompts: unset them (set_regions(None)) first")
+
+    def _place_regions(self, B, L=None):
+        """Hand every cross-attention layer (k, vt, ldk, vt_batch_stride, {N: w_level}, R) -- its slices of the stacked projection of all context
+        sets -- for a batch of B rows -> the layers to clear afterwards."""
+        rg = self._regions
+        if rg is None:
+            return []
+        if B not in (rg["rows"], 2 * rg["rows"]):
+            raise ValueError(f"the batch ({B}) is neither the regions' rows ({rg['rows']}: cond) nor twice that (cond, then uncond)")
+        if L is not None and L != rg["L"]:
+            raise ValueError(f"the context has {L} tokens, the regions' contexts {rg['L']}")
+        layers = self._cross_attn_layers()
+        R = rg["R"]
+        k, vt = rg["k"][:B * R * rg["L"]], rg["vt"][:B * R]
+        w = {n: t[:B * R] for n, t in rg["w"].items()}
+        off = 0
+        for m in layers:
+            c = m.inner_dim
+            m._region_pre = (k[:, off:off + c], vt[:, off:off + c, :], k.stride(0), vt.stride(0), w, R)
+            off += c
+        return layers
+
     def _control_hint(self, B, hw):
         """The hint features for a batch of B rows (row b: hint b % B0), expanded once per batch size and kept."""
         ctrl = self._control
@@ -653,17 +747,21 @@ class UNetModel(nn.Module):
         context [B,L,ctx] fp16 -> (eps [B,H,W,out_channels] fp16, captured activations)."""
         if capture_layers:
             self._refuse_ip("capturing cross-attention activations")
+            self._refuse_regions("capturing cross-attention activations")
         emb = self._embed(timesteps)   # SiLU(emb) (its only consumers are the emb_layers) + all 22 projections
         kv_layers = self._project_context_all(context)
-        ip_layers = []
+        ip_layers, rg_layers = [], []
         try:
             ip_layers = self._place_ip(x_nhwc.shape[0])
+            rg_layers = self._place_regions(x_nhwc.shape[0], None if context is None else context.shape[1])
             return self._hip_blocks(x_nhwc, emb, context, img_mask, capture_layers, timesteps)
         finally:
             for m in kv_layers:
                 m._kv_pre = None
             for m in ip_layers:
                 m._ip_pre = None
+            for m in rg_layers:
+                m._region_pre = None
 
     def _cross_attn_layers(self):
         out = []
@@ -682,10 +780,7 @@ class UNetModel(nn.Module):
         layers = self._cross_attn_layers()
         if not layers or context is None:
             return []
-        ws = [m.to_k.weight for m in layers] + [m.to_v.weight for m in layers]
-        if not hasattr(self, "_kv_all_cache"):
-            self._kv_all_cache = _PackCache()
-        pack = self._kv_all_cache.get(ws, lambda: ops.pack_matrix(torch.cat([w.detach() for w in ws], 0), None, ws[0].device))
+        pack = _kv_all_pack(self, layers)
         B, L, cc = context.shape
         sc = pack.N // 2
         k_all, vt_all = ops.gemm(context.reshape(B * L, cc), pack, rows_per_batch=L, split_col=sc)
@@ -752,6 +847,7 @@ class UNetModel(nn.Module):
         self._refuse_motion("the trunk cache (hip_tail)")
         self._refuse_control("the trunk cache (hip_tail)")
         self._refuse_ip("the trunk cache (hip_tail)")
+        self._refuse_regions("the trunk cache (hip_tail)")
         h, skips = trunk
         emb = self._embed(timesteps)
         kv_layers = self._project_context_all(context)
@@ -785,6 +881,7 @@ class UNetModel(nn.Module):
         self._refuse_motion("hip_train")
         self._refuse_control("hip_train")
         self._refuse_ip("hip_train")
+        self._refuse_regions("hip_train")
         emb = self._embed(timesteps)
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
@@ -805,6 +902,7 @@ class UNetModel(nn.Module):
         self._refuse_motion("hip_train_trunk")
         self._refuse_control("hip_train_trunk")
         self._refuse_ip("hip_train_trunk")
+        self._refuse_regions("hip_train_trunk")
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
         for module in self.input_blocks:
@@ -826,6 +924,7 @@ class UNetModel(nn.Module):
         self._refuse_motion("the trunk cache (hip_trunk)")
         self._refuse_control("the trunk cache (hip_trunk)")
         self._refuse_ip("the trunk cache (hip_trunk)")
+        self._refuse_regions("the trunk cache (hip_trunk)")
         kv_layers = self._project_context_all(context)
         try:
             hs = []
@@ -912,6 +1011,7 @@ class UNetModel(nn.Module):
             self._refuse_motion("the captured / score-rewrite path")
             self._refuse_control("the captured / score-rewrite path")
             self._refuse_ip("the captured / score-rewrite path")
+            self._refuse_regions("the captured / score-rewrite path")
             if extra_info is None:
                 raise ValueError("extra_info must be a dict on the capture / score-rewrite path")
             if capture:
@@ -924,6 +1024,7 @@ class UNetModel(nn.Module):
             self._refuse_motion("training")
             self._refuse_control("training")
             self._refuse_ip("training")
+            self._refuse_regions("training")
             gs = float((extra_info or {}).get("res_hidden_states_gradscale", 1) or 1)
             lora = (extra_info or {}).get("_ffn_lora_adapters")           # set by UNetWrapper when use_ffn_lora is on
             return _UNetFunction.apply(self, x, timesteps, context, img_mask, gs, lora, *[t[3] for t in lora_param_order(lora)])

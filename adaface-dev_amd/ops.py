@@ -1326,6 +1326,64 @@ def ip_attention_add(o, q, k, v, *, B: int, N: int, heads: int, d: int, ip_scale
     return o
 
 
+REGION_MAX = 8                    # af_region_attention: 1 <= R <= 8 context sets per batch item (the base prompt + up to 7 regions)
+REGION_MAX_TOKENS = 80            # ... of 1 <= L <= 80 context tokens each
+
+
+def region_attention(q, k, vt, w, *, B: int, R: int, N: int, L: int, heads: int, d: int, ldk: int, scale=None, out=None):
+    """Regional prompts: o [B*N, heads*d] = sum_r w[b*R+r, i] * softmax(scale q k_r^T) v_r over the R context sets of each batch item, blended in
+    fp32 and rounded once (af_region_attention, one launch, no workspace).  q [B*N, >= heads*d] token rows; context set (b, r) is batch item
+    b*R+r of k (rows (b*R+r)*L + t, row stride ``ldk``) and vt ([B*R, heads*d, >= L], V transposed; a row slice of a taller tensor keeps its
+    strides) -- the operands of ``attention`` with the sets as batch items, so a layer reads its slice of one stacked projection in place.  w fp32 [B*R, >= N] with contiguous rows.  A weight that is exactly 0 is a select: that query
+    takes nothing from the set (NaN included), and a 128-query tile with no nonzero weight for a set does not read it.  ``out``: write there
+    ([B*N, >= heads*d] rows) instead of a new tensor.  Returns o."""
+    _chk_f16_rows(q, "region_attention.q")
+    Cn = heads * d
+    if out is None:
+        out = torch.empty((B * N, Cn), dtype=F16, device=q.device)
+    _chk_f16_rows(out, "region_attention.out")
+    for t, name in ((q, "q"), (out, "out")):
+        if t.shape[0] != B * N or t.shape[1] < Cn:
+            raise RuntimeError(f"region_attention.{name}: expected [{B * N}, >= {Cn}], got {tuple(t.shape)}")
+    for t, name in ((k, "k"), (vt, "vt")):
+        if t.dtype != F16 or not t.is_cuda or t.stride(-1) != 1:
+            raise RuntimeError(f"region_attention.{name}: expected an fp16 device tensor with a contiguous last dim, got {t.dtype} {t.device} strides {t.stride()}")
+    if w.dtype != torch.float32 or not w.is_cuda or w.dim() != 2 or w.stride(1) != 1 or w.shape[0] != B * R or w.shape[1] < N:
+        raise RuntimeError(f"region_attention.w: expected an fp32 device matrix [{B * R}, >= {N}] with contiguous rows, got {w.dtype} {w.device} "
+                           f"{tuple(w.shape)} strides {w.stride()}")
+    if vt.dim() != 3 or vt.shape[0] != B * R or vt.shape[1] != Cn:
+        raise RuntimeError(f"region_attention.vt: expected [{B * R}, {Cn}, ldv], got {tuple(vt.shape)}")
+    _launch("af_region_attention", _p(q), _ld(q), _p(k), int(ldk), _p(vt), vt.stride(1), vt.stride(0), _p(w), w.stride(0), _p(out), _ld(out),
+            B, R, N, L, heads, d, float(d ** -0.5 if scale is None else scale))
+    return out
+
+
+def region_level_sizes(H: int, W: int):
+    """Tokens of the four U-Net levels of an H x W-pixel image (latent side = pixels / 8, then / 1, 2, 4, 8)."""
+    n0 = (H // 8) * (W // 8)
+    return [n0, n0 // 4, n0 // 16, n0 // 64]
+
+
+def region_weights(masks, beta: float, H: Optional[int] = None, W: Optional[int] = None, device=None):
+    """The region weights of all four U-Net levels in one launch (af_region_weights).  masks uint8 [R-1, H, W] on the device (0 .. 255, 255 = the
+    region; None with H, W and device for no region: R = 1) -> (w fp32 [R, sum N_l], [views [R, N_l] of its column ranges, l = 0 .. 3]).
+    Each mask is area-averaged onto the level's token grid, then w_r = (1 - beta) m_r / max(1, s), w_0 = beta + (1 - beta)(1 - min(1, s)),
+    s = sum_r m_r.  H and W are multiples of 64."""
+    if masks is not None:
+        if masks.dtype != torch.uint8 or not masks.is_cuda or masks.dim() != 3 or not masks.is_contiguous():
+            raise RuntimeError(f"region_weights.masks: expected a contiguous uint8 device tensor [R-1, H, W], got {masks.dtype} {masks.device} {tuple(masks.shape)}")
+        H, W, device = masks.shape[1], masks.shape[2], masks.device
+    R = 1 if masks is None else masks.shape[0] + 1
+    sizes = region_level_sizes(H, W)
+    w = torch.empty((R, sum(sizes)), dtype=torch.float32, device=device)
+    _launch("af_region_weights", _p(masks), R, H, W, float(beta), _p(w), w.stride(0))
+    levels, off = [], 0
+    for n in sizes:
+        levels.append(w[:, off:off + n])
+        off += n
+    return w, levels
+
+
 def softmax_rows_bwd(p, dp):
     """ds = p * (dp - rowsum(p * dp)) for fp16 [rows, L] probabilities and their gradient."""
     _chk_f16(p, "softmax_rows_bwd.p")

@@ -494,6 +494,30 @@ int af_temporal_attention(const void* qkv, int ld, void* out, int B, int F, int 
  * AF_E_BADARG (before any launch): NULL pointer, a size or stride outside the above, an operand of 2^31 elements or more. */
 int af_ip_attention_add(void* o, int ldo, const void* q, int ldq, const void* k, int ldk, int64_t k_bstride, const void* v, int ldv,
                         int64_t v_bstride, int B, int N, int T, int heads, int d, float scale, float ip_scale, void* stream);
+/* Regional prompts: the cross-attention core over R context sets per batch item, blended per query under the region weights w:
+ *   o[b*N+i, h*d+j] = fp16( sum_r w[b*R+r, i] * sum_t softmax_t(scale * <q[b,i,h,:], k[b,r,t,h,:]>) * v[b,r,t,h,j] ),  t over L tokens, r over R sets.
+ * q fp16 [B*N, ldq], o fp16 [B*N, ldo], w fp32 [B*R, ldw] (ldw >= N).  Context set (b, r) is batch item b*R+r of k and vt, addressed exactly as
+ * af_attention_strided addresses its batch items: k rows (b*R+r)*L + t with row stride ldk, vt the values TRANSPOSED ([heads*d, ldv] per item,
+ * key index contiguous, ldv >= L) at element stride vt_batch_stride (>= heads*d*ldv), so a layer reads its slice of ONE stacked projection of
+ * all layers in place.  1 <= R <= 8, 1 <= L <= 80, d % 8 == 0, 8 <= d <= 160, any N >= 1; ldq / ldo / ldk / ldv and vt_batch_stride are multiples
+ * of 8, ldq / ldo / ldk >= heads*d, pointers 16-byte aligned, B and heads <= 65535.
+ * One launch, no workspace.  fp32 scores (the scale is applied to them, q is not rescaled in fp16), softmax, normalisation by the fp32 row sum and
+ * weighted sum over the sets; P is rounded to fp16 once as the MFMA operand, o once.
+ * The zero weight is a SELECT, not a multiply: a query with w[b*R+r, i] == 0 receives nothing from set (b, r) whatever its K / V hold (Inf and
+ * NaN included); a 128-query tile whose weights for r are all 0 does not read K_r / V_r (so those need not even be written); a query whose
+ * weights are all 0 gets zeros.  The skip is decided per workgroup before any barrier of the set's iteration (every wave reduces the tile's
+ * weights itself), so no barrier sits in divergent control flow.
+ * AF_E_BADARG (before any launch): NULL pointer, a size or stride outside the above, an operand of 2^31 elements or more. */
+int af_region_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldv, int64_t vt_batch_stride,
+                        const void* w, int ldw, void* o, int ldo, int B, int R, int N, int L, int heads, int d, float scale, void* stream);
+/* The region weights of all four U-Net levels from R-1 uint8 masks [R-1, H, W] (0 .. 255, 255 = the region) in ONE launch: the masks are
+ * area-averaged onto each level's token grid (cells of 8, 16, 32, 64 pixels: m_r = sum / (255 * area), the integer sum exact) and, with
+ * s = sum_{r>=1} m_r:  w_r = (1 - beta) * m_r / max(1, s) for r >= 1,  w_0 = beta + (1 - beta) * (1 - min(1, s)).
+ * w fp32 [R, ldw]: level l (0 .. 3, N_l = (H/8 >> l) * (W/8 >> l) tokens, row-major) at columns [off_l, off_l + N_l), off_0 = 0,
+ * off_l = off_{l-1} + N_{l-1}; ldw >= 85 * H * W / 4096.  A cell no pixel of mask r touches holds exactly 0.0 in row r.
+ * H and W multiples of 64 in 64 .. 16384, 1 <= R <= 8 (masks may be NULL at R == 1), 0 <= beta <= 1, masks 8-byte aligned.
+ * AF_E_BADARG (before any launch) otherwise. */
+int af_region_weights(const void* masks, int R, int H, int W, float beta, void* w, int ldw, void* stream);
 /* its backward, ds = p * (dp - rowsum(p * dp)), for the decode-with-grad path of the ArcFace alignment loss (ddpm.py:2511-2535
  * differentiates through decode_first_stage_with_grad, ddpm.py:899-908) */
 int af_softmax_rows_bwd(const void* p, const void* dp, void* ds, int64_t rows, int L, void* stream);
