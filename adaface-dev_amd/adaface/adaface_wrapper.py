@@ -281,7 +281,7 @@ class AdaFaceWrapper(nn.Module):
                  enable_static_img_suffix_embs=None, device="cuda", is_training=False,
                  tokenizer=None, text_encoder=None, ldm=None, vae=None, id2ada_prompt_encoder=None, unet_config=None, clip_config=None,
                  lcm_lora_path=None, lcm_lora_scale=1.0, face_id_extractor=None, face_detector=None, motion_module_path=None,
-                 beta_schedule="linear", upscaler=None, face_restorer=None, controlnet=None, ip_adapter=None, ip_image_encoder=None):
+                 beta_schedule="linear", upscaler=None, face_restorer=None, controlnet=None, ip_adapter=None, ip_image_encoder=None, freeu=None):
         super().__init__()
         if pipeline_name not in ("text2img", "img2img", "inpaint", None):
             raise NotImplementedError(f"pipeline {pipeline_name!r}: only the SD-1.5 text2img, img2img and inpaint paths (and None = face "
@@ -341,6 +341,7 @@ class AdaFaceWrapper(nn.Module):
         self.__dict__["motion_module"] = None     # a MotionModule (load_motion_module); not a submodule: it is on the U-Net only inside forward(num_frames=F)
         self.__dict__["controlnet"] = None        # a ControlNet (load_controlnet); not a submodule: it is on the U-Net only inside forward(control_image=...)
         self.__dict__["ip_adapter"] = None        # an IPAdapter (load_ip_adapter); not a submodule: it is on the U-Net only inside forward(ip_adapter_image= / ip_adapter_face_id=)
+        self.__dict__["freeu"] = None             # enable_freeu's values ({"b1", "b2", "s1", "s2", "version"}) while FreeU is on; they live on the U-Net (set_freeu)
         self.__dict__["ip_image_encoder"] = None  # the CLIP ViT-H/14 VisionTransformer of a kind="clip" adapter; not a submodule
         self.vae = vae
         self.img_prompt_embs = None
@@ -365,6 +366,16 @@ class AdaFaceWrapper(nn.Module):
             self.load_ip_adapter(ip_adapter, ip_image_encoder)
         elif ip_image_encoder is not None:
             raise ValueError("ip_image_encoder is given without ip_adapter")
+        if freeu is not None and freeu is not False:
+            if freeu is True:
+                self.enable_freeu()
+            elif isinstance(freeu, dict):
+                unknown = sorted(set(freeu) - {"b1", "b2", "s1", "s2", "version"})
+                if unknown:
+                    raise ValueError(f"freeu: unknown key(s) {unknown}: expected b1, b2, s1, s2, version")
+                self.enable_freeu(**freeu)
+            else:
+                raise ValueError(f"freeu must be None, True or a dict(b1=, b2=, s1=, s2=, version=), got {type(freeu).__name__}")
 
     # ------------------------------------------------------------------ checkpoints
     def load_base_model(self, base_model_path):
@@ -404,6 +415,27 @@ class AdaFaceWrapper(nn.Module):
         self.__dict__["motion_module"] = None
         if self.ldm is not None:
             self.ldm.model.diffusion_model.set_motion(None)
+
+    def enable_freeu(self, s1=0.9, s2=0.2, b1=1.5, b2=1.6, version=2):
+        """FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net"; INTEGRATION.md "FreeU") for every later ``forward``: the decoder's
+        backbone features are boosted (b1 / b2) and its skip features lose part of their lowest spatial frequencies (s1 / s2), in the two
+        stages whose backbone has 4 x / 2 x ``model_channels`` channels.  Argument order and names are diffusers' ``enable_freeu``; the
+        defaults are the authors' values for SD-1.5.  ``version=1`` boosts by the constant b instead of the per-pixel map.  It works on all
+        pipelines and samplers and beside ``num_frames``, ``control_image``, an IP-Adapter, regions, both passes of ``hires_size`` and face
+        repainting: every U-Net call of the wrapper goes through the walk that applies it.  Bad values are a ValueError naming the
+        argument, before any GPU work."""
+        from ..ldm.modules.diffusionmodules.openaimodel import check_freeu_values
+        if self.ldm is None:
+            raise RuntimeError("pipeline_name=None builds the face encoder only: there is no U-Net to run FreeU in")
+        cfg = check_freeu_values("enable_freeu", b1, b2, s1, s2, version)
+        self.ldm.model.diffusion_model.set_freeu(**cfg)
+        self.__dict__["freeu"] = cfg
+        return cfg
+
+    def disable_freeu(self):
+        self.__dict__["freeu"] = None
+        if self.ldm is not None:
+            self.ldm.model.diffusion_model.set_freeu(None)
 
     def load_controlnet(self, path_or_net):
         """A ControlNet for ``forward(..., control_image=...)`` (ldm/modules/diffusionmodules/controlnet.py; INTEGRATION.md "ControlNet"): a

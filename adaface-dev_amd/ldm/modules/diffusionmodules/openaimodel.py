@@ -302,6 +302,32 @@ def _kv_all_pack(net, layers):
     return net._kv_all_cache.get(ws, lambda: ops.pack_matrix(torch.cat([w.detach() for w in ws], 0), None, ws[0].device))
 
 
+def check_freeu_values(who, b1, b2, s1, s2, version):
+    """ValueError (naming ``who`` and the argument) unless b1, b2, s1, s2 are finite numbers >= 0 and version is 1 or 2 -> the checked dict."""
+    out = {}
+    for name, v in (("b1", b1), ("b2", b2), ("s1", s1), ("s2", s2)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{who}: {name} must be a number, got {type(v).__name__}")
+        v = float(v)
+        if v != v or v in (float("inf"), float("-inf")) or v < 0:
+            raise ValueError(f"{who}: {name} must be finite and >= 0, got {v}")
+        out[name] = v
+    if isinstance(version, bool) or version not in (1, 2):
+        raise ValueError(f"{who}: version must be 1 or 2, got {version!r}")
+    out["version"] = int(version)
+    return out
+
+
+def freeu_plan(model_channels, h_channels, cfg):
+    """FreeU's per-output-block plan: for each output block, given the channels of h in front of its skip concatenation, (b1, s1) where h has
+    4 x model_channels, (b2, s2) where it has 2 x model_channels, None elsewhere (the authors' patch of the ldm UNetModel keys the stages by
+    channel count).  ``cfg``: set_freeu's state or None (every block None).  Pure: no device, no module."""
+    if cfg is None:
+        return [None] * len(h_channels)
+    stage = {4 * model_channels: (cfg["b1"], cfg["s1"]), 2 * model_channels: (cfg["b2"], cfg["s2"])}
+    return [stage.get(c) for c in h_channels]
+
+
 class UNetModel(nn.Module):
     """The SD-1.5 U-Net with the reference's constructor signature (openaimodel.py:444-469).
     Only the options SD-1.5 uses are implemented; the others raise at construction."""
@@ -380,9 +406,11 @@ class UNetModel(nn.Module):
         )
 
         self.output_blocks = nn.ModuleList([])
+        self._out_h_channels = []                # channels of h in front of each output block's skip concatenation (freeu_plan keys FreeU's stages by them)
         for level, mult in list(enumerate(channel_mult))[::-1]:
             for i in range(num_res_blocks + 1):
                 ich = input_block_chans.pop()
+                self._out_h_channels.append(ch)
                 layers = [ResBlock(ch + ich, time_embed_dim, dropout, out_channels=model_channels * mult, dims=dims,
                                    use_checkpoint=use_checkpoint)]
                 ch = model_channels * mult
@@ -401,6 +429,7 @@ class UNetModel(nn.Module):
         self.__dict__["_control"] = None         # set_control's state ({"net", "hint", "scale", "expanded", "active"}) while it holds a ControlNet; not a submodule either
         self.__dict__["_ip"] = None              # set_ip_adapter's state ({"adapter", "rows", "T", "kv", "scale", "active"}) while it holds an IP-Adapter; not a submodule
         self.__dict__["_regions"] = None         # set_regions' state ({"rows", "R", "L", "k", "vt", "w"}) while regional prompts are set; not a submodule
+        self.__dict__["_freeu"] = None           # set_freeu's state ({"b1", "b2", "s1", "s2", "version"}) while FreeU is set; plain numbers, not in the state dict
         self.__dict__["_motion"] = None          # (MotionModule, num_frames) while set_motion holds one; not a submodule: the state dict stays SD-1.5's
 
     # ------------------------------------------------------------------ reference flag plumbing
@@ -686,6 +715,25 @@ class UNetModel(nn.Module):
         if self._regions is not None:
             raise NotImplementedError(f"{what} is not built with regional prompts: unset them (set_regions(None)) first")
 
+    # ------------------------------------------------------------------ FreeU (csrc/af_freeu.hip)
+    def set_freeu(self, b1, b2=None, s1=None, s2=None, version=2):
+        """Run ``hip`` with FreeU (Si et al.): in front of every output block whose h has 4 x model_channels (b1, s1) or 2 x model_channels
+        (b2, s2) channels, the first half of h's channels is boosted and the skip loses part of its lowest spatial frequencies (``freeu_plan``,
+        ``ops.freeu``: two launches per block, in place).  The joined skip is what is filtered when a ControlNet is set.  ``set_freeu(None)``
+        restores the plain walk exactly, and so do four values of 1 (no launch).  Not built for training and the trunk cache (refused by name)."""
+        if b1 is None:
+            self.__dict__["_freeu"] = None
+            return
+        self.__dict__["_freeu"] = check_freeu_values("set_freeu", b1, b2, s1, s2, version)
+
+    def freeu_plan(self):
+        """[(b, s) | None] per output block for the FreeU state that is set (``freeu_plan`` of this module)."""
+        return freeu_plan(self.model_channels, self._out_h_channels, self._freeu)
+
+    def _refuse_freeu(self, what):
+        if self._freeu is not None:
+            raise NotImplementedError(f"{what} is not built with FreeU: unset it (set_freeu(None)) first")
+
     def _place_regions(self, B, L=None):
         """Hand every cross-attention layer (k, vt, ldk, vt_batch_stride, {N: w_level}, R) -- its slices of the stacked projection of all context
         sets -- for a batch of B rows -> the layers to clear afterwards."""
@@ -832,8 +880,15 @@ class UNetModel(nn.Module):
         if layer_idx in capture_layers:
             collect(self.middle_block, h)
         layer_idx += 1
+        fu = self._freeu
+        plan = self.freeu_plan() if fu is not None else [None] * len(self.output_blocks)
         for n, module in enumerate(self.output_blocks):
-            h = run(module, "output", n, SkipCat((h, hs.pop())))
+            skip = hs.pop()
+            if plan[n] is not None:
+                # FreeU, in place on both: h is the previous block's output and the skip an input block's (or the ControlNet's joined one), each
+                # read by nobody else from here on; ops.freeu drops the producers' GroupNorm statistics of what it rewrites
+                h, skip = ops.freeu(h, skip, plan[n][0], plan[n][1], fu["version"], out_h=h, out_skip=skip)
+            h = run(module, "output", n, SkipCat((h, skip)))
             if layer_idx in capture_layers:
                 collect(module, h)
             layer_idx += 1
@@ -848,6 +903,7 @@ class UNetModel(nn.Module):
         self._refuse_control("the trunk cache (hip_tail)")
         self._refuse_ip("the trunk cache (hip_tail)")
         self._refuse_regions("the trunk cache (hip_tail)")
+        self._refuse_freeu("the trunk cache (hip_tail)")
         h, skips = trunk
         emb = self._embed(timesteps)
         kv_layers = self._project_context_all(context)
@@ -882,6 +938,7 @@ class UNetModel(nn.Module):
         self._refuse_control("hip_train")
         self._refuse_ip("hip_train")
         self._refuse_regions("hip_train")
+        self._refuse_freeu("hip_train")
         emb = self._embed(timesteps)
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
@@ -903,6 +960,7 @@ class UNetModel(nn.Module):
         self._refuse_control("hip_train_trunk")
         self._refuse_ip("hip_train_trunk")
         self._refuse_regions("hip_train_trunk")
+        self._refuse_freeu("hip_train_trunk")
         saved_in, saved_out, hs = [], [], []
         h = x_nhwc
         for module in self.input_blocks:
@@ -925,6 +983,7 @@ class UNetModel(nn.Module):
         self._refuse_control("the trunk cache (hip_trunk)")
         self._refuse_ip("the trunk cache (hip_trunk)")
         self._refuse_regions("the trunk cache (hip_trunk)")
+        self._refuse_freeu("the trunk cache (hip_trunk)")
         kv_layers = self._project_context_all(context)
         try:
             hs = []
@@ -945,6 +1004,7 @@ class UNetModel(nn.Module):
     def hip_bwd_trunk(self, saved, dh, dskips_tail, need_dx=True, res_gradscale=1.0):
         """Backward of hip_train_trunk: dh = gradient of h, dskips_tail[i] = gradient of the i-th popped skip (already scaled by the
         tail where the live path scales it) or None.  Same walk as hip_bwd."""
+        self._refuse_freeu("hip_bwd_trunk")
         saved_in, saved_mid, saved_out, ctx_shape = saved
         n_in, n_out, n_tail = len(self.input_blocks), len(self.output_blocks), len(dskips_tail)
         d, dctx = dh, None
@@ -971,6 +1031,7 @@ class UNetModel(nn.Module):
         decoder are added to the encoder's output gradients as the walk reaches them; `res_gradscale` multiplies the
         gradient of the skips consumed by output blocks >= num_res_blocks + 1 (the live path's
         res_hidden_states_gradscale on diffusers up_blocks[1:], diffusers_attn_lora_capture.py:382-396, 606-609)."""
+        self._refuse_freeu("hip_bwd")
         saved_in, saved_mid, saved_out, h_last, st, ctx_shape = saved
         d = self.out[0].hip_bwd(h_last, st, self.out[2].hip_dgrad(deps_nhwc), silu=True)
         dctx = None
@@ -1012,6 +1073,7 @@ class UNetModel(nn.Module):
             self._refuse_control("the captured / score-rewrite path")
             self._refuse_ip("the captured / score-rewrite path")
             self._refuse_regions("the captured / score-rewrite path")
+            self._refuse_freeu("the captured / score-rewrite path")
             if extra_info is None:
                 raise ValueError("extra_info must be a dict on the capture / score-rewrite path")
             if capture:
@@ -1025,6 +1087,7 @@ class UNetModel(nn.Module):
             self._refuse_control("training")
             self._refuse_ip("training")
             self._refuse_regions("training")
+            self._refuse_freeu("training")
             gs = float((extra_info or {}).get("res_hidden_states_gradscale", 1) or 1)
             lora = (extra_info or {}).get("_ffn_lora_adapters")           # set by UNetWrapper when use_ffn_lora is on
             return _UNetFunction.apply(self, x, timesteps, context, img_mask, gs, lora, *[t[3] for t in lora_param_order(lora)])

@@ -1384,6 +1384,69 @@ def region_weights(masks, beta: float, H: Optional[int] = None, W: Optional[int]
     return w, levels
 
 
+_freeu_ws = {}
+
+
+def _chk_freeu(h, skip, b, s, version):
+    _chk_f16(h, "freeu.h")
+    _chk_f16(skip, "freeu.skip")
+    if h.dim() != 4 or skip.dim() != 4 or h.shape[:3] != skip.shape[:3] or h.device != skip.device:
+        raise RuntimeError(f"freeu: h and skip must be [B, H, W, C] and [B, H, W, Cs] on one device, got {tuple(h.shape)} and {tuple(skip.shape)}")
+    return (h.shape[0], h.shape[1], h.shape[2], h.shape[3], skip.shape[3], float(b), float(s), int(version))
+
+
+def freeu_workspace_size(B: int, H: int, W: int, C: int, Cs: int) -> int:
+    """fp32 elements of the workspace af_freeu_stats / af_freeu_apply share at these sizes (the library's own count)."""
+    return _checked("af_freeu_ws_floats", B, H, W, C, Cs)
+
+
+def freeu_stats(h, skip, b: float, s: float, version: int = 2, ws=None):
+    """The statistics pass of FreeU (af_freeu_stats, one launch; none when b == s == 1): the pixel means of h with their (lo, hi) partials and the
+    seven shifted sums of every skip plane, into ``ws`` (fp32, >= freeu_workspace_size; default: the per-device scratch).  Returns ws."""
+    args = _chk_freeu(h, skip, b, s, version)
+    if ws is None:
+        ws = _grow_scratch(_freeu_ws, h.device, freeu_workspace_size(*args[:5]), torch.float32)
+    elif ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous():
+        raise RuntimeError(f"freeu_stats.ws: expected a contiguous fp32 device tensor, got {ws.dtype} {ws.device}")
+    _launch("af_freeu_stats", _p(h), _p(skip), _p(ws), ws.numel(), *args)
+    return ws
+
+
+def freeu(h, skip, b: float, s: float, version: int = 2, out_h=None, out_skip=None):
+    """FreeU on the inputs of a skip concatenation, h [B, H, W, C] and skip [B, H, W, Cs] (contiguous NHWC fp16) -> (h', skip'): the first C/2
+    channels of h times (b - 1) * mhat + 1 (version 2; b for version 1), every skip plane with its lowest spatial frequencies scaled by s
+    (include/adaface_hip.h).  Two launches, af_freeu_stats and af_freeu_apply; b == 1 or s == 1 leaves that tensor alone (it is returned as it
+    is, or copied when another ``out_*`` is given), and b == s == 1 launches nothing.  ``out_h`` / ``out_skip``: write there; the input itself
+    (in place) is allowed and, for h, spares the copy of the untouched upper half of the channels.  Statistics a producer attached to a tensor
+    written in place are dropped (the write bypasses torch's version counter)."""
+    args = _chk_freeu(h, skip, b, s, version)
+    b, s = args[5], args[6]
+    for o, x, name in ((out_h, h, "out_h"), (out_skip, skip, "out_skip")):
+        if o is not None and o is not x:
+            _chk_f16(o, f"freeu.{name}")
+            if o.shape != x.shape or o.device != x.device:
+                raise RuntimeError(f"freeu.{name}: expected {tuple(x.shape)} on {x.device}, got {tuple(o.shape)} on {o.device}")
+    do_h, do_s = b != 1.0, s != 1.0
+    if do_h or do_s:
+        ws = freeu_stats(h, skip, b, s, version)          # refuses bad b / s / version / sizes before anything is written
+    oh = h if not do_h and out_h is None else (torch.empty_like(h) if out_h is None else out_h)
+    os_ = skip if not do_s and out_skip is None else (torch.empty_like(skip) if out_skip is None else out_skip)
+    Cn = h.shape[3]
+    if oh is not h:
+        if do_h:
+            oh[..., Cn // 2:] = h[..., Cn // 2:]           # the kernel writes the first half only
+        else:
+            oh.copy_(h)
+    if os_ is not skip and not do_s:
+        os_.copy_(skip)
+    if do_h or do_s:
+        _launch("af_freeu_apply", _p(h), _p(skip), _p(ws), ws.numel(), _p(oh), _p(os_), *args)
+        for o, x, did in ((oh, h, do_h), (os_, skip, do_s)):
+            if did and o is x and getattr(o, "_gn_partials", None) is not None:
+                o._gn_partials = None
+    return oh, os_
+
+
 def softmax_rows_bwd(p, dp):
     """ds = p * (dp - rowsum(p * dp)) for fp16 [rows, L] probabilities and their gradient."""
     _chk_f16(p, "softmax_rows_bwd.p")

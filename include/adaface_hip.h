@@ -518,6 +518,30 @@ int af_region_attention(const void* q, int ldq, const void* k, int ldk, const vo
  * H and W multiples of 64 in 64 .. 16384, 1 <= R <= 8 (masks may be NULL at R == 1), 0 <= beta <= 1, masks 8-byte aligned.
  * AF_E_BADARG (before any launch) otherwise. */
 int af_region_weights(const void* masks, int R, int H, int W, float beta, void* w, int ldw, void* stream);
+/* FreeU (Si et al.) on the two inputs of a decoder skip concatenation, h [B, H, W, C] and skip [B, H, W, Cs], contiguous NHWC fp16, per sample:
+ *   h[p, :C/2] *= f[p];   version 2: f = (b - 1) * mhat + 1, mhat = (m - lo) / (hi - lo), m[p] = fp32 mean of h[p, :] over all C channels, lo / hi
+ *                         its min / max over the sample's pixels, mhat = 0 where hi == lo (the authors' code gives NaN there);   version 1: f = b
+ *   skip plane (sample, channel) x -> y[h, w] = x[h, w] + (s - 1) / (H W) * sum_{u in Uh, v in Uw} (A_uv cos phi + B_uv sin phi),
+ *                         phi = 2 pi (u h / H + v w / W), A_uv = sum x cos phi, B_uv = sum x sin phi, Uh = {0, -1 mod H}, Uw = {0, -1 mod W}
+ * (the authors' Fourier_filter(skip, threshold = 1, scale = s) in closed form: four bins, two when a side is 1, one at 1 x 1).
+ * af_freeu_stats makes one pass over h and skip and leaves in ws (fp32, af_freeu_ws_floats(B, H, W, C, Cs) floats, 16-byte aligned) the pixel
+ * means with per-wave (lo, hi) partials (version 2 and b != 1 only) and, when s != 1, per (sample, skip channel) the plane's first pixel (the pivot
+ * the sums are shifted by) and the seven sums as one partial per slice of the pixels; af_freeu_apply adds the partials in slice order and writes
+ *   h_out[:, :C/2] = sat(h * f)   (channels C/2 .. C of h_out are NOT written: in place, h_out == h, is the intended form)   and
+ *   skip_out = sat(skip + (s - 1) / (H W) * low)   (skip_out == skip is allowed).
+ * No atomics and no hand-off between workgroups inside a launch: two runs are bit-identical.  fp32 throughout, each output rounded to fp16 once;
+ * finite values saturate at +-65504, NaN and Inf stay.  A NaN pixel mean makes lo and hi, and with them that sample's h_out[:, :C/2], NaN; a skip
+ * plane that holds a NaN or an Inf is NaN everywhere (as its DFT is); nothing crosses from one sample to another or from one plane to another.
+ * s == 1: skip is not read and skip_out not written (no NaN from 0 * Inf); b == 1: h is not read and h_out not written; both 1: no launch.
+ * 1 <= B <= 65535; 1 <= H, W <= 128; C % 16 == 0 in 16 .. 16384; Cs % 8 == 0 in 8 .. 16384; B*H*W*C and B*H*W*Cs below 2^31 (the kernels index
+ * with 64 bits; the limit is the library's common one); b and s finite and >= 0; version 1 or 2; all pointers 16-byte aligned.
+ * AF_E_BADARG before any launch, outputs and workspace untouched: anything else, a NULL pointer, ws_floats below af_freeu_ws_floats.
+ * Both calls of a pair take the same sizes, b, s and version.  No allocation, no host synchronisation: the pair can be captured. */
+int64_t af_freeu_ws_floats(int B, int H, int W, int C, int Cs);
+int af_freeu_stats(const void* h, const void* skip, void* ws, int64_t ws_floats, int B, int H, int W, int C, int Cs, float b, float s, int version,
+                   void* stream);
+int af_freeu_apply(const void* h, const void* skip, const void* ws, int64_t ws_floats, void* h_out, void* skip_out, int B, int H, int W, int C,
+                   int Cs, float b, float s, int version, void* stream);
 /* its backward, ds = p * (dp - rowsum(p * dp)), for the decode-with-grad path of the ArcFace alignment loss (ddpm.py:2511-2535
  * differentiates through decode_first_stage_with_grad, ddpm.py:899-908) */
 int af_softmax_rows_bwd(const void* p, const void* dp, void* ds, int64_t rows, int L, void* stream);
